@@ -7,7 +7,17 @@ K8s replica scaling). One "request" = a batched /score call of 1024 rows
 (BASELINE config 2), scored through the full engine path: host encode →
 pinned H2D → HIP forest/iforest/drift kernels → D2H → p-value conversion.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+--dump-outputs DIR also writes the last timed step's outputs as DIR/*.npy so
+two builds can be compared output for output (request bodies are seeded, so
+equal arguments mean equal inputs). --full is where measurements beyond the
+headline figure belong; there are none today. The packed model is cached
+under $CREDITCORE_CACHE_DIR (default ~/.cache/creditcore), so only the first
+run trains it. For repeatable figures a single-rank run pins itself to a
+block of 16 neighbouring CPUs (CREDITCORE_BENCH_PIN_CPUS, 0 = off) and turns
+the cyclic garbage collector off for the timed steps.
 
 For N>1 the driver launches this under torch.distributed.run; each rank
 scores its own request stream (weak scaling). Rank 0 prints one JSON line.
@@ -26,6 +36,33 @@ BENCH_MODEL = {"n_estimators": 500, "max_depth": 16, "criterion": "gini"}
 TRAIN_ROWS = 20_000
 
 
+def bench_cache_dir() -> str:
+    """Where the packed bench model is cached between runs:
+    $CREDITCORE_CACHE_DIR, else ~/.cache/creditcore (a per-user location
+    that outlives the process's temp dir), else the temp dir when the home
+    directory is not writable."""
+    d = os.environ.get("CREDITCORE_CACHE_DIR") or os.path.join(
+        os.path.expanduser("~"), ".cache", "creditcore"
+    )
+    try:
+        os.makedirs(d, exist_ok=True)
+        if os.access(d, os.W_OK):
+            return d
+    except OSError:
+        pass
+    import tempfile
+
+    return tempfile.gettempdir()
+
+
+def packed_path(cache_dir: str) -> str:
+    algo = BENCH_MODEL.get("algo", "rf")
+    return os.path.join(
+        cache_dir,
+        f"bench_packed_{algo}_{BENCH_MODEL['n_estimators']}x{BENCH_MODEL['max_depth']}_{TRAIN_ROWS}.npz",
+    )
+
+
 def _build_packed(cache_dir: str, seed: int = 2024):
     """Train the reference-scale model once (rank 0), pack, cache as npz."""
     from creditcore import train as T
@@ -40,10 +77,7 @@ def _build_packed(cache_dir: str, seed: int = 2024):
     from creditcore.schema import FEATURES, TARGET
 
     algo = BENCH_MODEL.get("algo", "rf")
-    path = os.path.join(
-        cache_dir,
-        f"bench_packed_{algo}_{BENCH_MODEL['n_estimators']}x{BENCH_MODEL['max_depth']}_{TRAIN_ROWS}.npz",
-    )
+    path = packed_path(cache_dir)
     if os.path.exists(path):
         return PackedModel.load(path), path
     df = make_uci_shaped_frame(n_rows=TRAIN_ROWS, seed=seed)
@@ -57,6 +91,26 @@ def _build_packed(cache_dir: str, seed: int = 2024):
     packed = PackedModel(**c, **o, **d)
     packed.save(path)
     return packed, path
+
+
+def _dump_outputs(out: dict, dump_dir: str) -> None:
+    """Write what one step of the timed path returned as <name>.npy
+    (float64): the /score response fields a client receives — predictions,
+    outliers, feature_drift_batch (values in schema feature order) — plus
+    the batch's categorical histogram the serving layer aggregates. A few
+    KB per array at any supported --rows, so nothing is sampled."""
+    import numpy as np
+
+    arrays = {}
+    if "response_bytes" in out:
+        for name, v in json.loads(bytes(out["response_bytes"])).items():
+            arrays[name] = list(v.values()) if isinstance(v, dict) else v
+    for name in ("predictions", "cat_hist"):
+        if name in out:
+            arrays[name] = out[name]
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(dump_dir, f"{name}.npy"), np.asarray(v, dtype=np.float64))
 
 
 def _free_port() -> int:
@@ -126,6 +180,13 @@ def main():
                    help="classifier family for the bench model")
     p.add_argument("--dump-steps", default="",
                    help="write per-step wall times (JSON list, rank 0) here")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step returned (rank 0) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (none today: the plain run already does "
+                        "only what requests/sec needs)")
     args = p.parse_args()
     if args.model_trees:
         BENCH_MODEL["n_estimators"] = args.model_trees
@@ -149,6 +210,26 @@ def main():
     if device == "cuda":
         # tolerate more ranks than GPUs (e.g. RCCL smoke tests on one GPU)
         local_rank = local_rank % max(torch.cuda.device_count(), 1)
+    pin = int(os.environ.get("CREDITCORE_BENCH_PIN_CPUS", "16"))
+    if pin > 0 and not distributed and hasattr(os, "sched_setaffinity"):
+        # Keep this process's threads (step loop, encoders, epilogue, HIP
+        # runtime) on one block of neighbouring cores. Left free to roam a
+        # 256-CPU two-socket host they settle into placements that differ
+        # by ~40% in step time and switch every few thousand steps, so
+        # 20000-step runs of the same build spread 7.3k-8.9k requests/s;
+        # on a 16-CPU block (with the collector off, below) five runs
+        # stayed within 1% (9.22k-9.32k). 0 disables; multi-rank runs are
+        # left to the launcher's placement.
+        allowed = sorted(os.sched_getaffinity(0))
+        if len(allowed) > pin:
+            try:  # CPU this thread last ran on (proc(5), field 39)
+                with open("/proc/self/stat") as f:
+                    cur = int(f.read().rsplit(")", 1)[1].split()[36])
+            except (OSError, ValueError, IndexError):
+                cur = allowed[0]
+            start = (allowed.index(cur) // pin) * pin if cur in allowed else 0
+            start = min(start, len(allowed) - pin)
+            os.sched_setaffinity(0, allowed[start:start + pin])
     if distributed:
         from datetime import timedelta
 
@@ -173,7 +254,7 @@ def main():
     from creditcore.data import make_request_batch
     from creditcore.engine import ScoringEngine
 
-    cache_dir = os.environ.get("TMPDIR", "/tmp")
+    cache_dir = bench_cache_dir()
     packed = None
     if rank == 0:
         # Train/pack in a SUBPROCESS so the scoring process stays clean:
@@ -181,12 +262,7 @@ def main():
         # parent's heap/threads in a state measured ~20-40% slower on the
         # subsequent timed loop (cold-run p50 0.145 ms vs 0.100 ms from a
         # pre-packed cache). Mirrors production: pack offline, serve loads.
-        algo = BENCH_MODEL.get("algo", "rf")
-        path = os.path.join(
-            cache_dir,
-            f"bench_packed_{algo}_{BENCH_MODEL['n_estimators']}x"
-            f"{BENCH_MODEL['max_depth']}_{TRAIN_ROWS}.npz",
-        )
+        path = packed_path(cache_dir)
         if not os.path.exists(path):
             import subprocess
 
@@ -242,6 +318,9 @@ def main():
         for i in range(4)
     ]
     with_drift = not args.no_drift
+    # the most recent step's return value (one reference, replaced every
+    # step, so nothing accumulates) — what --dump-outputs writes
+    last: dict = {}
 
     if args.no_pipeline or (args.rows <= 256 and device == "cuda"):
         # latency mode: the fully-native single-call path (parse -> graph ->
@@ -250,6 +329,7 @@ def main():
         def one_step(i: int):
             out = engine.score_json_full(pool[i % len(pool)])
             assert out["rows"] == args.rows
+            last["out"] = out
             return out
 
         def run_steps(k: int, step_times=None):
@@ -283,6 +363,7 @@ def main():
 
         def _post_step(out, nums, i, outs, step_times, t_prev):
             assert out["rows"] == args.rows
+            last["out"] = out
             if (
                 drift_sync is not None
                 and "cat_hist" in out
@@ -403,7 +484,11 @@ def main():
             torch.cuda.synchronize()
 
     sync()
-    if os.environ.get("CREDITCORE_BENCH_GC_DISABLE") == "1":
+    # The cyclic collector is off for the timed steps (the loop builds no
+    # reference cycles; refcounting still frees every response): its
+    # pauses fell at different steps from run to run.
+    # CREDITCORE_BENCH_GC_DISABLE=0 leaves it on.
+    if os.environ.get("CREDITCORE_BENCH_GC_DISABLE", "1") == "1":
         import gc
 
         gc.collect()
@@ -439,6 +524,12 @@ def main():
         n_live_ranks = 1
         n_gpus = 1
     requests_per_sec = n_live_ranks * args.steps / elapsed
+
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's request is pool[(steps - 1) % 4] (pipelined
+        # mode: (warmup + steps - 1) % 4 — burn-in runs in multiples of 64),
+        # so equal arguments dump equal inputs' outputs
+        _dump_outputs(last["out"], args.dump_outputs)
 
     if rank == 0:
         print(

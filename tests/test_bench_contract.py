@@ -38,7 +38,8 @@ def _env(tmp_path):
     return dict(
         os.environ,
         PYTHONPATH=REPO + os.pathsep + os.environ.get("PYTHONPATH", ""),
-        TMPDIR=str(tmp_path),  # isolate the packed-model cache
+        TMPDIR=str(tmp_path),
+        CREDITCORE_CACHE_DIR=str(tmp_path),  # isolate the packed-model cache
     )
 
 
@@ -58,6 +59,43 @@ def test_bench_single_process_contract(tmp_path):
     assert d["higher_is_better"] is True and d["scaling"] == "weak"
     assert d["value"] > 0 and d["ms_per_step"] > 0
     assert d["config"]["parallelism"] == "dp1"
+
+
+@pytest.mark.slow
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float .npy,
+    identical between two runs with the same arguments (--full included,
+    which must not change the headline path)."""
+    import numpy as np
+
+    from creditcore.schema import FEATURES
+
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = subprocess.run(
+            [sys.executable, os.path.join(REPO, "bench.py"), "--device", "cpu",
+             "--steps", "3", "--warmup", "1", "--rows", "64",
+             "--model-trees", "12", "--model-depth", "4",
+             "--dump-outputs", str(d)] + extra,
+            capture_output=True, text=True, timeout=540, env=_env(tmp_path), cwd=REPO,
+        )
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = _last_json_line(r.stdout)
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert {"predictions", "outliers", "feature_drift_batch"} <= set(a)
+    assert set(a) == set(b)
+    assert a["predictions"].shape == (64,) and a["outliers"].shape == (64,)
+    assert a["feature_drift_batch"].shape == (len(FEATURES),)
+    assert ((a["predictions"] >= 0) & (a["predictions"] <= 1)).all()
+    assert a["predictions"].std() > 0  # real scores, not a constant fill
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64)
+        assert np.isfinite(a[k]).all()
+        np.testing.assert_array_equal(a[k], b[k])
 
 
 @pytest.mark.slow
