@@ -33,15 +33,38 @@ def timed(fn, iters=50, warmup=10):
     return s.elapsed_time(e) / iters * 1e3  # µs
 
 
+def timed_samples(fns: dict, rounds=15, iters=20, warmup=10) -> dict:
+    """Interleaved rounds in one process: every round times each variant, so
+    clock/thermal drift hits all of them alike. Returns per-variant
+    {median, min, max} in µs over the rounds."""
+    for fn in fns.values():
+        timed(fn, iters=warmup, warmup=0)
+    samples = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            samples[k].append(timed(fn, iters=iters, warmup=0))
+    return {
+        k: {
+            "median_us": round(float(np.median(v)), 2),
+            "min_us": round(min(v), 2),
+            "max_us": round(max(v), 2),
+        }
+        for k, v in samples.items()
+    }
+
+
 def main():
     import torch
 
     from creditcore.ops import gpu
-    from creditcore.pack import PackedModel, encode_batch
+    from creditcore.pack import encode_batch
     from creditcore.data import make_request_batch
 
+    import bench as flagship
+
     ext = gpu.ext()
-    p = PackedModel.load("/tmp/bench_packed_500x16_20000.npz")
+    # the flagship bench model (500 trees x depth 16), from its cache
+    p, _ = flagship._build_packed(flagship.bench_cache_dir())
     dev = torch.device("cuda", 0)
 
     medians = torch.from_numpy(p.medians).to(dev)
@@ -94,6 +117,46 @@ def main():
         for v in (1, 2, 3, 4):
             c = ext.forest_ilp_bench(d_codes, d_nums, cls_nodes, cls_off, fc, fk, medians, v)
             results[f"forest_ilp_parity b={b} v={v}"] = float((a - c).abs().max().item())
+
+    # attributions next to the scorer's classifier kernel at the same shape:
+    # forest_contrib vs forest_kernel<false> (ilp=0, the kernel
+    # score_forest_pipeline launches for the classifier), interleaved rounds
+    if p.cls_node_value is None:
+        results["forest_contrib"] = "skipped: cached bench model predates node values"
+    else:
+        node_value = torch.from_numpy(p.cls_node_value).to(dev)
+        b = 1024
+        codes, nums = encode_batch(make_request_batch(b, seed=b), p.vocabs)
+        d_codes = torch.from_numpy(codes).to(dev)
+        d_nums = torch.from_numpy(nums).to(dev)
+        def contrib(block_target=None):
+            extra = () if block_target is None else (block_target,)
+            return lambda: ext.forest_contrib(
+                d_codes, d_nums, cls_nodes, node_value, cls_off, fc, fk,
+                medians, p.cls_kind, *extra,
+            )
+
+        stats = timed_samples(
+            {
+                "forest_contrib": contrib(),
+                # A/B of the grid size: fewer blocks = more trees per thread
+                # = fewer atomics, against fewer waves in flight
+                **{f"forest_contrib blocks={t}": contrib(t) for t in (2048, 1024, 256)},
+                "forest_cls": lambda: ext.forest_ilp_bench(
+                    d_codes, d_nums, cls_nodes, cls_off, fc, fk, medians, 0
+                ),
+                "forest_pipeline": lambda: ext.score_forest_pipeline(
+                    d_codes, d_nums, cls_nodes, cls_off, fc, fk, medians,
+                    p.n_onehot, if_nodes, if_off,
+                    p.if_denom, p.if_offset, p.if_threshold,
+                ),
+            }
+        )
+        for k, v in stats.items():
+            results[f"{k} b={b} samples"] = v
+        results[f"forest_contrib/forest_cls b={b}"] = round(
+            stats["forest_contrib"]["median_us"] / stats["forest_cls"]["median_us"], 3
+        )
 
     print(json.dumps(results, indent=2))
 

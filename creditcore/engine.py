@@ -25,6 +25,7 @@ to CPU: the HIP extension must be present (ops/gpu.py).
 
 from __future__ import annotations
 
+import threading
 import time
 
 import numpy as np
@@ -34,10 +35,57 @@ from .pack import N_CAT, N_NUM, PackedModel, encode_batch
 from .schema import FEATURES
 
 
+class ExplainUnavailable(RuntimeError):
+    """The model was packed without per-node expected values
+    (PackedModel.cls_node_value is None), so attributions cannot be computed."""
+
+
+class ExplainTooLarge(ValueError):
+    """An explain call exceeded ScoringEngine.EXPLAIN_MAX_ROWS."""
+
+
+def _check_forest_tables(p: PackedModel) -> None:
+    """Host-side bounds check of everything forest_contrib_kernel indexes
+    with model data (the kernel trusts its tables): node features, child
+    links, the one-hot/numeric source columns and the value array length."""
+    nodes, off = p.cls_nodes, p.cls_tree_offsets
+    n_feat = len(p.feat_col)
+    ok = (
+        nodes.ndim == 2
+        and nodes.shape[1] == 4
+        and len(p.cls_node_value) == len(nodes)
+        and len(p.feat_code) == n_feat
+        and len(p.medians) == N_NUM
+        and len(off) >= 2
+        and off[0] == 0
+        and off[-1] == len(nodes)
+        and bool((np.diff(off) > 0).all())
+    )
+    if ok:
+        feat = nodes[:, 0]
+        split = feat >= 0
+        size = np.repeat(np.diff(off), np.diff(off))  # own tree's node count
+        local = np.arange(len(nodes)) - np.repeat(off[:-1], np.diff(off))
+        cat = p.feat_code >= 0
+        ok = (
+            bool((feat < n_feat).all())
+            # BFS order: children come after their parent, so walks terminate
+            and bool((nodes[split, 2:] > local[split, None]).all())
+            and bool((nodes[split, 2:] < size[split, None]).all())
+            and bool((p.feat_col >= 0).all())
+            and bool((p.feat_col[cat] < N_CAT).all())
+            and bool((p.feat_col[~cat] < N_NUM).all())
+        )
+    if not ok:
+        raise ValueError("packed classifier forest is malformed; refusing to explain")
+
+
 class ScoringEngine:
     # K-S kernel LDS sort capacity (csrc MAX_DRIFT_ROWS) — the hardware
     # ceiling; the per-engine cap (config drift_max_batch) can only lower it
     HW_DRIFT_MAX_ROWS = 16384
+    # per-call row cap of explain_arrays / explain_records / POST /explain
+    EXPLAIN_MAX_ROWS = 16384
 
     def __init__(
         self,
@@ -54,6 +102,8 @@ class ScoringEngine:
             drift_max_rows or self.HW_DRIFT_MAX_ROWS, self.HW_DRIFT_MAX_ROWS
         )
         self._gpu = None
+        self._explain_lock = threading.Lock()
+        self._explain_dev = None  # lazily uploaded device tensors (explain)
         if device == "cuda":
             self._init_gpu()
 
@@ -147,6 +197,101 @@ class ScoringEngine:
             out["cat_hist"] = cat_hist
             out["ks_d"] = ks_d
         return out
+
+    # ------------------------------------------------------- attributions
+    def explain_arrays(self, codes: np.ndarray, nums: np.ndarray) -> dict:
+        """Per-row prediction-path (Saabas) attributions for the classifier.
+
+        Returns ``contributions`` f64[B, 23] in schema.FEATURES order,
+        ``base_value``, ``output_space`` ("probability" for the averaging
+        forests, "log_odds" for gradient boosting) and ``predictions``
+        (base + row sum, through the sigmoid for log-odds) — the scoring
+        kernels are not run. base_value + contributions.sum(1) is the model
+        output by construction."""
+        p = self.packed
+        if p.cls_node_value is None:
+            raise ExplainUnavailable(
+                "model was packed without per-node expected values; "
+                "re-pack it from the trained pipeline to enable attributions"
+            )
+        b = len(codes)
+        if b > self.EXPLAIN_MAX_ROWS:
+            raise ExplainTooLarge(
+                f"explain is capped at {self.EXPLAIN_MAX_ROWS} rows per call (got {b})"
+            )
+        codes = np.ascontiguousarray(codes, dtype=np.int16).reshape(b, N_CAT)
+        nums = np.ascontiguousarray(nums, dtype=np.float32).reshape(b, N_NUM)
+        if self.device == "cuda":
+            contrib = self._explain_gpu(codes, nums)
+        else:
+            contrib = cpu_ref.forest_contrib_cpu(
+                p, codes, cpu_ref.impute_nums(p, nums)
+            )
+        base = float(p.cls_base_value)
+        raw = base + contrib.sum(axis=1)
+        log_odds = int(getattr(p, "cls_kind", 0)) == 1
+        return {
+            "contributions": contrib,
+            "base_value": base,
+            "output_space": "log_odds" if log_odds else "probability",
+            "predictions": 1.0 / (1.0 + np.exp(-raw)) if log_odds else raw,
+        }
+
+    def _explain_gpu(self, codes: np.ndarray, nums: np.ndarray) -> np.ndarray:
+        import torch
+
+        ext = self._gpu["ext"]
+        dev = torch.device("cuda", self.device_index)
+        # The lock covers the lazy upload and the call: concurrent explains on
+        # one replica serialize; scoring is untouched (no shared state).
+        with self._explain_lock:
+            m = self._explain_dev
+            if m is None:
+                p = self.packed
+                _check_forest_tables(p)
+                # Own device copies of the model tensors — the session keeps
+                # its buffers private, so cls_nodes sits in HBM twice
+                # (16 B/node; accepted for an explain path that never
+                # touches session state).
+                m = {
+                    "cls_nodes": torch.from_numpy(
+                        np.ascontiguousarray(p.cls_nodes, dtype=np.int32)
+                    ).to(dev),
+                    "cls_node_value": torch.from_numpy(
+                        np.ascontiguousarray(p.cls_node_value, dtype=np.float32)
+                    ).to(dev),
+                    "cls_off": torch.from_numpy(
+                        np.ascontiguousarray(p.cls_tree_offsets, dtype=np.int32)
+                    ).to(dev),
+                    "feat_col": torch.from_numpy(
+                        np.ascontiguousarray(p.feat_col, dtype=np.int32)
+                    ).to(dev),
+                    "feat_code": torch.from_numpy(
+                        np.ascontiguousarray(p.feat_code, dtype=np.int32)
+                    ).to(dev),
+                    "medians": torch.from_numpy(
+                        np.ascontiguousarray(p.medians, dtype=np.float32)
+                    ).to(dev),
+                }
+                self._explain_dev = m
+            with torch.cuda.device(dev):
+                out = ext.forest_contrib(
+                    torch.from_numpy(codes).to(dev),
+                    torch.from_numpy(nums).to(dev),
+                    m["cls_nodes"],
+                    m["cls_node_value"],
+                    m["cls_off"],
+                    m["feat_col"],
+                    m["feat_code"],
+                    m["medians"],
+                    int(getattr(self.packed, "cls_kind", 0)),
+                )
+                return out.cpu().numpy()  # D2H copy synchronizes the stream
+
+    def explain_records(self, records) -> dict:
+        """explain_arrays on a request body (list of dicts / DataFrame)."""
+        codes, nums = encode_batch(records, self.packed.vocabs)
+        return self.explain_arrays(codes, nums)
 
     def encode_json_body(self, body: bytes) -> tuple:
         """Parse a raw /score JSON body into (codes, nums) with the native C

@@ -84,6 +84,61 @@ def score_forest_cpu(
     return (s / packed.cls_n_trees).astype(np.float64)
 
 
+def forest_contrib_cpu(
+    packed: PackedModel, codes: np.ndarray, nums_imp: np.ndarray
+) -> np.ndarray:
+    """Per-row prediction-path (Saabas) attributions, f64[B, N_CAT + N_NUM]
+    in schema feature order.
+
+    Every split on a row's path credits v[child taken] - v[node] to the
+    source column of the split feature (one-hot features fold back onto
+    their categorical column). Same traversal semantics as score_forest_cpu
+    (f32 compares); differences and sums are f64. Scaled by 1/T for the
+    averaging forests, 1 for gradient boosting, so that
+    cls_base_value + contrib.sum(1) is the model output (probability, or
+    log-odds for GBT)."""
+    if packed.cls_node_value is None:
+        raise ValueError(
+            "model was packed without per-node expected values "
+            "(cls_node_value is None); re-pack it to compute attributions"
+        )
+    nodes, offsets = packed.cls_nodes, packed.cls_tree_offsets
+    fc, fk = packed.feat_col, packed.feat_code
+    bits = nodes[:, 1].view(np.float32)
+    val = packed.cls_node_value.astype(np.float64)
+    n_rows = len(codes)
+    n_src = N_CAT + N_NUM
+    T = len(offsets) - 1
+    cur = np.repeat(offsets[:-1].astype(np.int64), n_rows)
+    base = cur.copy()
+    rows = np.tile(np.arange(n_rows, dtype=np.int64), T)
+    acc = np.zeros(n_rows * n_src, dtype=np.float64)
+    alive = np.arange(T * n_rows, dtype=np.int64)
+    while len(alive):
+        nidx = cur[alive]
+        feat = nodes[nidx, 0]
+        split = feat >= 0
+        alive, nidx, feat = alive[split], nidx[split], feat[split]
+        if not len(alive):
+            break
+        r = rows[alive]
+        col = fc[feat].astype(np.int64)
+        code = fk[feat]
+        cat = code >= 0
+        v = np.empty(len(alive), dtype=np.float32)
+        if cat.any():
+            v[cat] = (codes[r[cat], col[cat]] == code[cat]).astype(np.float32)
+        if (~cat).any():
+            v[~cat] = nums_imp[r[~cat], col[~cat]]
+        go_left = v <= bits[nidx]
+        nxt = base[alive] + np.where(go_left, nodes[nidx, 2], nodes[nidx, 3])
+        src = np.where(cat, col, N_CAT + col)
+        np.add.at(acc, r * n_src + src, val[nxt] - val[nidx])
+        cur[alive] = nxt
+    scale = 1.0 if getattr(packed, "cls_kind", 0) == 1 else 1.0 / T
+    return acc.reshape(n_rows, n_src) * scale
+
+
 def score_iforest_cpu(
     packed: PackedModel, nums_imp: np.ndarray
 ) -> tuple[np.ndarray, np.ndarray]:

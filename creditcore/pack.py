@@ -62,10 +62,14 @@ def _average_path_length(n: np.ndarray) -> np.ndarray:
 
 
 def _pack_sklearn_tree(
-    tree, leaf_values: np.ndarray, feature_remap: np.ndarray | None = None
-) -> np.ndarray:
+    tree,
+    leaf_values: np.ndarray,
+    feature_remap: np.ndarray | None = None,
+    with_values: bool = False,
+):
     """Repack one sklearn tree_ into BFS node-SoA [n,4] int32 (bits column
-    stores f32 as raw bits)."""
+    stores f32 as raw bits). With ``with_values`` also return the per-node
+    expected value f32[n] in the same BFS order (see ``_node_values``)."""
     cl = tree.children_left
     cr = tree.children_right
     feat = tree.feature
@@ -107,7 +111,36 @@ def _pack_sklearn_tree(
             nodes[k, 2] = int(new_idx[cl[i]])
             nodes[k, 3] = int(new_idx[cr[i]])
     nodes[:, 1] = f32.view(np.int32)
+    if with_values:
+        w = np.asarray(tree.weighted_n_node_samples, dtype=np.float64)[order]
+        return nodes, _node_values(nodes, w)
     return nodes
+
+
+def _node_values(nodes: np.ndarray, weights: np.ndarray) -> np.ndarray:
+    """Cover-weighted expected value per node of one BFS-packed tree.
+
+    Leaf: the stored f32 payload, bit-identical. Internal node:
+    (w_l*v_l + w_r*v_r)/(w_l + w_r) in f64 over the already-rounded f32 child
+    values, then rounded to f32. sklearn's own internal ``tree_.value`` is not
+    used: for gradient boosting it holds mean residuals, which are not on the
+    line-searched leaf scale. BFS order puts children after their parent, so
+    one reverse sweep is bottom-up."""
+    n = len(nodes)
+    vals = np.zeros(n, dtype=np.float32)
+    bits = nodes[:, 1].view(np.float32)
+    for k in range(n - 1, -1, -1):
+        if nodes[k, 0] == LEAF:
+            vals[k] = bits[k]
+            continue
+        l, r = int(nodes[k, 2]), int(nodes[k, 3])
+        wl, wr = float(weights[l]), float(weights[r])
+        if wl + wr <= 0.0:  # degenerate cover: plain mean
+            wl = wr = 1.0
+        vals[k] = np.float32(
+            (wl * np.float64(vals[l]) + wr * np.float64(vals[r])) / (wl + wr)
+        )
+    return vals
 
 
 def _concat_trees(tree_nodes: list[np.ndarray]) -> tuple[np.ndarray, np.ndarray]:
@@ -156,6 +189,12 @@ class PackedModel:
     lin_weight: np.ndarray | None = None  # f32[F_total]
     lin_bias: float = 0.0
 
+    # optional attribution state: cover-weighted expected value per classifier
+    # node, index-aligned with cls_nodes, and the model's expected output
+    # (RF/ET: mean of root values; GBT: cls_bias + sum of root values)
+    cls_node_value: np.ndarray | None = None  # f32[n_nodes]
+    cls_base_value: float = 0.0
+
     meta: dict = field(default_factory=dict)
 
     @property
@@ -172,8 +211,13 @@ class PackedModel:
 
     # -- persistence (fast serving start without sklearn unpickling) --------
     def save(self, path: str) -> None:
+        extra = {}
+        if self.cls_node_value is not None:
+            extra["cls_node_value"] = self.cls_node_value
+            extra["cls_base_value"] = self.cls_base_value
         np.savez_compressed(
             path,
+            **extra,
             vocabs=np.asarray(
                 ["\x00".join(v) for v in self.vocabs], dtype=object
             ),
@@ -228,6 +272,10 @@ class PackedModel:
             ref_cat_offsets=z["ref_cat_offsets"],
             lin_weight=lw if lw.size else None,
             lin_bias=float(z["lin_bias"]),
+            cls_node_value=z["cls_node_value"] if "cls_node_value" in z else None,
+            cls_base_value=(
+                float(z["cls_base_value"]) if "cls_base_value" in z else 0.0
+            ),
         )
 
 
@@ -257,7 +305,7 @@ def pack_classifier_pipeline(pipeline) -> dict:
         feat_col.append(col)
         feat_code.append(-1)
 
-    trees = []
+    trees, values = [], []
     cls_kind, cls_bias = 0, 0.0
     if hasattr(clf, "loss_") or type(clf).__name__ == "GradientBoostingClassifier":
         cls_kind = 1
@@ -276,7 +324,9 @@ def pack_classifier_pipeline(pipeline) -> dict:
         for est in clf.estimators_[:, 0]:
             t = est.tree_
             leaf_raw = np.asarray(t.value, dtype=np.float64)[:, 0, 0] * lr
-            trees.append(_pack_sklearn_tree(t, leaf_raw))
+            nd, nv = _pack_sklearn_tree(t, leaf_raw, with_values=True)
+            trees.append(nd)
+            values.append(nv)
     else:
         for est in clf.estimators_:
             t = est.tree_
@@ -285,8 +335,15 @@ def pack_classifier_pipeline(pipeline) -> dict:
             sums[sums == 0] = 1.0
             leaf_p1 = value[:, 0, 1] / sums  # fraction of class 1 (normalised
             # either way: sklearn >=1.4 already stores fractions)
-            trees.append(_pack_sklearn_tree(t, leaf_p1))
+            nd, nv = _pack_sklearn_tree(t, leaf_p1, with_values=True)
+            trees.append(nd)
+            values.append(nv)
     nodes, offsets = _concat_trees(trees)
+    roots = np.asarray([float(v[0]) for v in values], dtype=np.float64)
+    if cls_kind == 1:
+        base_value = float(cls_bias + roots.sum())
+    else:
+        base_value = float(roots.sum() / len(roots))
 
     return {
         "vocabs": vocabs,
@@ -298,6 +355,8 @@ def pack_classifier_pipeline(pipeline) -> dict:
         "cls_tree_offsets": offsets,
         "cls_kind": cls_kind,
         "cls_bias": cls_bias,
+        "cls_node_value": np.concatenate(values),
+        "cls_base_value": base_value,
     }
 
 

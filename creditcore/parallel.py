@@ -86,6 +86,10 @@ def broadcast_packed(
         meta["has_lin"] = packed.lin_weight is not None
         if meta["has_lin"]:
             meta["lin_shape"] = list(packed.lin_weight.shape)
+        meta["has_node_value"] = packed.cls_node_value is not None
+        if meta["has_node_value"]:
+            meta["node_value_shape"] = list(packed.cls_node_value.shape)
+            meta["cls_base_value"] = float(packed.cls_base_value)
         obj = [meta]
     else:
         obj = [None]
@@ -116,13 +120,32 @@ def broadcast_packed(
         dist.broadcast(lw, src=src, group=group)
         lin_weight = lw.cpu().numpy()
 
+    # optional per-node expected values (attributions); models packed
+    # without them broadcast as before
+    cls_node_value = None
+    if meta["has_node_value"]:
+        if is_src:
+            nv = torch.from_numpy(
+                np.ascontiguousarray(packed.cls_node_value.astype(np.float32, copy=False))
+            ).to(device)
+        else:
+            nv = torch.empty(meta["node_value_shape"], dtype=torch.float32, device=device)
+        dist.broadcast(nv, src=src, group=group)
+        cls_node_value = nv.cpu().numpy()
+
     if is_src:
         return packed
     kw = {name: tensors[name].cpu().numpy() for name, _ in _ARRAY_FIELDS}
     for f in _META_FIELDS:
         kw[f] = meta[f]
     kw.pop("meta", None)
-    return PackedModel(lin_weight=lin_weight, meta=meta["meta"], **kw)
+    return PackedModel(
+        lin_weight=lin_weight,
+        cls_node_value=cls_node_value,
+        cls_base_value=meta.get("cls_base_value", 0.0),
+        meta=meta["meta"],
+        **kw,
+    )
 
 
 class DriftSync:

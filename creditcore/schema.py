@@ -122,6 +122,26 @@ class ModelOutput(BaseModel):
     feature_drift_batch: FeatureBatchDrift
 
 
+class Reason(BaseModel):
+    """One reason code: a feature and its attribution for one row."""
+
+    feature: str
+    contribution: float
+
+
+class ExplainOutput(BaseModel):
+    """POST /explain response: per-row prediction-path (Saabas) attributions.
+    base_value + sum(contributions[r]) is the model output for row r in
+    ``output_space`` ("probability", or "log_odds" for gradient boosting)."""
+
+    output_space: str
+    base_value: float
+    features: list[str]
+    predictions: list[float]
+    contributions: list[list[float]]
+    top_reasons: list[list[Reason]]
+
+
 # The one-record CI smoke-test fixture (reference app/sample-request.json).
 SAMPLE_REQUEST: list[dict] = [
     {

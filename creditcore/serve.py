@@ -24,13 +24,13 @@ from contextlib import asynccontextmanager
 from itertools import count
 
 import numpy as np
-from fastapi import FastAPI, HTTPException, Request, Response
+from fastapi import FastAPI, HTTPException, Query, Request, Response
 
 from .config import ServeConfig
 from .batching import MicroBatcher
-from .engine import ScoringEngine, load_engine
+from .engine import ExplainUnavailable, ScoringEngine, load_engine
 from .pack import encode_batch
-from .schema import FEATURES, LoanApplicant, ModelOutput
+from .schema import FEATURES, ExplainOutput, LoanApplicant, ModelOutput
 from .utils import logging as reqlog
 from .utils.metrics import Metrics
 
@@ -98,6 +98,25 @@ def admin_authorized(
 
         return presented is not None and secrets.compare_digest(presented, cfg.admin_token)
     return client_host is None or client_host in _LOOPBACK_HOSTS
+
+
+def top_reasons(contrib: np.ndarray, top_k: int) -> list[list[dict]]:
+    """Per row, the up-to-top_k features with the largest strictly positive
+    contribution (pushing toward default), descending, ties by feature index."""
+    if top_k <= 0:
+        return [[] for _ in range(len(contrib))]
+    # stable sort on the negated values keeps index order among ties
+    order = np.argsort(-contrib, axis=1, kind="stable")[:, :top_k]
+    out = []
+    for row, idxs in zip(contrib, order):
+        out.append(
+            [
+                {"feature": FEATURES[j], "contribution": float(row[j])}
+                for j in idxs
+                if row[j] > 0.0
+            ]
+        )
+    return out
 
 
 class ReplicaPool:
@@ -491,6 +510,68 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
     async def score(request: Request):
         """Alias — BASELINE.json names the endpoint /score."""
         return _json_response(await _predict_impl(await request.body()))
+
+    @app.post("/explain", response_model=ExplainOutput, openapi_extra=_openapi_extra)
+    async def explain(
+        request: Request,
+        top_k: int = Query(3, ge=0, le=len(FEATURES)),
+    ):
+        """Per-row feature attributions ("reason codes") for the classifier:
+        prediction-path (Saabas) contributions per input feature, plus the
+        up-to-top_k features pushing each row toward default. One attempt on
+        one live replica; bypasses the micro-batcher."""
+        import asyncio
+
+        metrics: Metrics = state["metrics"]
+        engines = state["engines"]
+        pool: ReplicaPool = state["pool"]
+        try:
+            codes, nums = _encode_body(await request.body(), engines[0])
+        except HTTPException:
+            raise
+        except (ValueError, TypeError) as e:
+            raise HTTPException(status_code=422, detail=f"bad record: {e}")
+        if len(codes) == 0:
+            raise HTTPException(status_code=400, detail="empty request batch")
+        if len(codes) > ScoringEngine.EXPLAIN_MAX_ROWS:
+            raise HTTPException(
+                status_code=413,
+                detail=f"/explain takes at most {ScoringEngine.EXPLAIN_MAX_ROWS} rows",
+            )
+        if engines[0].packed.cls_node_value is None:
+            raise HTTPException(
+                status_code=501,
+                detail="the served model was packed without per-node expected "
+                "values; re-pack it to enable /explain",
+            )
+        try:
+            idx = pool.pick()
+        except RuntimeError:
+            metrics.observe_error()
+            raise HTTPException(status_code=503, detail="no healthy replicas")
+        t0 = time.perf_counter()
+        try:
+            out = await asyncio.get_running_loop().run_in_executor(
+                None, engines[idx].explain_arrays, codes, nums
+            )
+            pool.report_ok(idx)
+        except ExplainUnavailable as e:
+            raise HTTPException(status_code=501, detail=str(e))
+        except Exception as e:
+            metrics.observe_error()
+            pool.report_fail(idx)
+            raise HTTPException(status_code=500, detail=f"explain failed: {e}")
+        contrib = out["contributions"]
+        payload = {
+            "output_space": out["output_space"],
+            "base_value": out["base_value"],
+            "features": list(FEATURES),
+            "predictions": np.asarray(out["predictions"]).tolist(),
+            "contributions": contrib.tolist(),
+            "top_reasons": top_reasons(contrib, top_k),
+        }
+        metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
+        return _json_response(payload)
 
     @app.get("/healthz")
     async def healthz(deep: bool = False):

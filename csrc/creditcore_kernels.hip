@@ -295,6 +295,90 @@ __global__ __launch_bounds__(BLOCK) void forest_kernel_dual(
   }
 }
 
+// Per-row feature attributions ("reason codes") for the classifier forest:
+// the prediction-path (Saabas) decomposition. A second walk over the same
+// nodes as forest_kernel<false> that, at every split, credits
+// v[child taken] - v[node] (v = cover-weighted expected value per node,
+// pack.py cls_node_value) to the SOURCE column of the split feature — one-hot
+// virtual features fold back onto their categorical column, numeric feature
+// j lands in column N_CAT + j. base + sum_c contrib[row, c] telescopes to the
+// model output.
+//
+// Same grid idea as forest_kernel (one thread per (row, tree-chunk), rows
+// staged in LDS column-major with fused imputation). The N_SRC per-thread
+// f64 accumulators are indexed by a runtime column, so they live in LDS
+// column-major (a register array would go to scratch); each thread touches
+// only its own slots — no barrier, no LDS atomics.
+//
+// LDS budget: this kernel runs 128-thread blocks (CONTRIB_BLOCK, NOT BLOCK):
+// 23*128*8 B accumulators + 9*128*2 B codes + 14*128*4 B nums = 33,024 B
+// static, under the 64 KiB static limit with several blocks per CU. At 256
+// threads the accumulators alone would need 47 KiB and the total 66 KiB.
+// The walk is one tree at a time: one extra 4-byte gather per step (the
+// child's value; the current node's value is carried along).
+#define CONTRIB_BLOCK 128
+#define N_SRC (N_CAT + N_NUM)
+
+__global__ __launch_bounds__(CONTRIB_BLOCK) void forest_contrib_kernel(
+    const short* __restrict__ codes,       // [B, N_CAT]
+    const float* __restrict__ nums,        // [B, N_NUM]
+    const float* __restrict__ medians,     // [N_NUM]
+    const int4* __restrict__ nodes,        // [n_nodes] {feat, bits, left, right}
+    const float* __restrict__ node_value,  // [n_nodes]
+    const int* __restrict__ tree_off,      // [T+1]
+    int n_trees,
+    const int* __restrict__ feat_col,      // [F]
+    const int* __restrict__ feat_code,     // [F]
+    int n_rows,
+    double scale,                          // 1/T (averaging forest) or 1 (GBT)
+    double* __restrict__ contrib)          // [B, N_SRC], pre-zeroed
+{
+  __shared__ double s_acc[N_SRC * CONTRIB_BLOCK];
+  __shared__ short s_codes[N_CAT * CONTRIB_BLOCK];
+  __shared__ float s_nums[N_NUM * CONTRIB_BLOCK];
+
+  const int tid = threadIdx.x;
+  const int row = blockIdx.x * CONTRIB_BLOCK + tid;
+  if (row >= n_rows) return;  // no barrier below: own LDS slots only
+
+#pragma unroll
+  for (int c = 0; c < N_CAT; ++c)
+    s_codes[c * CONTRIB_BLOCK + tid] = codes[(size_t)row * N_CAT + c];
+#pragma unroll
+  for (int c = 0; c < N_NUM; ++c) {
+    const float v = nums[(size_t)row * N_NUM + c];
+    s_nums[c * CONTRIB_BLOCK + tid] = isnan(v) ? medians[c] : v;
+  }
+#pragma unroll
+  for (int c = 0; c < N_SRC; ++c) s_acc[c * CONTRIB_BLOCK + tid] = 0.0;
+
+  for (int t = blockIdx.y; t < n_trees; t += gridDim.y) {
+    const int base = tree_off[t];
+    int4 nd = nodes[base];
+    float v_cur = node_value[base];
+    while (nd.x >= 0) {
+      const int col = feat_col[nd.x];
+      const int code = feat_code[nd.x];
+      const float v =
+          (code >= 0) ? ((s_codes[col * CONTRIB_BLOCK + tid] == (short)code) ? 1.0f : 0.0f)
+                      : s_nums[col * CONTRIB_BLOCK + tid];
+      const int next = base + ((v <= __int_as_float(nd.y)) ? nd.z : nd.w);
+      nd = nodes[next];
+      const float v_next = node_value[next];
+      const int src = (code >= 0) ? col : (N_CAT + col);
+      s_acc[src * CONTRIB_BLOCK + tid] += (double)v_next - (double)v_cur;
+      v_cur = v_next;
+    }
+  }
+
+  double* out = contrib + (size_t)row * N_SRC;
+#pragma unroll
+  for (int c = 0; c < N_SRC; ++c) {
+    const double a = s_acc[c * CONTRIB_BLOCK + tid];
+    if (a != 0.0) atomicAdd(&out[c], a * scale);
+  }
+}
+
 // 4-tree ILP + optional transposed grid (blockIdx.x = tree chunk so the
 // dispatcher's id%8 XCD placement gives adjacent chunks to different XCDs,
 // keeping each XCD's L2 on a tree subset). Experimental A/B variants.
@@ -823,6 +907,64 @@ std::vector<torch::Tensor> score_forest_pipeline(
   HIP_CHECK(hipGetLastError());
 
   return {proba, iscore, outlier};
+}
+
+// Prediction-path attributions f64[B, 23] for the classifier forest
+// (forest_contrib_kernel). Stateless: not part of ScoreSession or any captured
+// graph and shares no staging with the scoring path; runs on the caller's
+// current stream, no host sync.
+torch::Tensor forest_contrib(
+    torch::Tensor codes, torch::Tensor nums,
+    torch::Tensor cls_nodes, torch::Tensor cls_node_value,
+    torch::Tensor cls_off,
+    torch::Tensor feat_col, torch::Tensor feat_code,
+    torch::Tensor medians, int64_t cls_kind, int64_t block_target)
+{
+  check_inputs(codes, nums);
+  TORCH_CHECK(block_target >= 1 && block_target <= 65535, "bad block_target");
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType st, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == codes.device(), name,
+                " must be on the inputs' GPU");
+    TORCH_CHECK(t.scalar_type() == st && t.is_contiguous(), name,
+                " has the wrong dtype or is not contiguous");
+  };
+  on_dev(nums, torch::kFloat32, "nums");
+  on_dev(cls_nodes, torch::kInt32, "cls_nodes");
+  on_dev(cls_node_value, torch::kFloat32, "cls_node_value");
+  on_dev(cls_off, torch::kInt32, "cls_off");
+  on_dev(feat_col, torch::kInt32, "feat_col");
+  on_dev(feat_code, torch::kInt32, "feat_code");
+  on_dev(medians, torch::kFloat32, "medians");
+  TORCH_CHECK(cls_nodes.dim() == 2 && cls_nodes.size(1) == 4, "cls_nodes must be [n, 4]");
+  TORCH_CHECK(cls_node_value.dim() == 1 && cls_node_value.size(0) == cls_nodes.size(0),
+              "cls_node_value must be index-aligned with cls_nodes");
+  TORCH_CHECK(feat_col.numel() == feat_code.numel(), "feat_col/feat_code size mismatch");
+  TORCH_CHECK(medians.numel() == N_NUM, "medians must have N_NUM entries");
+  TORCH_CHECK(cls_off.numel() >= 2, "forest has no trees");
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)codes.get_device());
+  const int B = (int)codes.size(0);
+  const int T = (int)cls_off.size(0) - 1;
+  auto contrib = torch::zeros({B, N_SRC},
+      torch::TensorOptions().dtype(torch::kFloat64).device(codes.device()));
+  if (B == 0) return contrib;
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  const int row_blocks = ceil_div(B, CONTRIB_BLOCK);
+  // Fewer tree-chunks than the scorer's grid: every chunk ends in up to 23
+  // f64 atomics per thread, so more trees per thread means fewer atomics
+  // (block_target is the A/B knob of bench/kernel_micro.py).
+  const int chunks = std::max(1, std::min(ceil_div((int)block_target, row_blocks), T));
+  const double scale = (cls_kind == 1) ? 1.0 : 1.0 / (double)T;
+  hipLaunchKernelGGL(forest_contrib_kernel, dim3(row_blocks, chunks),
+      dim3(CONTRIB_BLOCK), 0, stream,
+      codes.data_ptr<short>(), nums.data_ptr<float>(), medians.data_ptr<float>(),
+      reinterpret_cast<const int4*>(cls_nodes.data_ptr<int>()),
+      cls_node_value.data_ptr<float>(), cls_off.data_ptr<int>(), T,
+      feat_col.data_ptr<int>(), feat_code.data_ptr<int>(), B, scale,
+      contrib.data_ptr<double>());
+  HIP_CHECK(hipGetLastError());
+  return contrib;
 }
 
 torch::Tensor forest_ilp_bench(
@@ -2425,6 +2567,12 @@ py::bytes response_epilogue(ScoreSession& s, int64_t slot64, int64_t b64,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("score_forest_pipeline", &score_forest_pipeline,
         "Forest classifier + isolation forest scoring (gfx950)");
+  m.def("forest_contrib", &forest_contrib,
+        "Per-row prediction-path feature attributions f64[B,23] (gfx950)",
+        py::arg("codes"), py::arg("nums"), py::arg("cls_nodes"),
+        py::arg("cls_node_value"), py::arg("cls_off"), py::arg("feat_col"),
+        py::arg("feat_code"), py::arg("medians"), py::arg("cls_kind"),
+        py::arg("block_target") = 512);
   m.def("drift_stats", &drift_stats,
         "Per-feature drift statistics: categorical histograms + K-S D (gfx950)");
   m.def("encode_records", &encode_records,
