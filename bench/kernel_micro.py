@@ -4,6 +4,7 @@ Sweeps launch configurations of the hot kernels on a real MI355X so the
 session picks measured-best settings:
 
     python bench/kernel_micro.py            # K-S sweep + forest timing
+    python bench/kernel_micro.py --shap-only   # the forest_shap section alone
 """
 
 from __future__ import annotations
@@ -71,8 +72,9 @@ def main():
     ref = torch.from_numpy(p.ref_sorted).to(dev)
     rs_off = torch.from_numpy(p.ref_sorted_offsets).to(dev)
 
+    shap_only = "--shap-only" in _sys.argv[1:]
     results = {}
-    for b in (1024, 4096, 16384):
+    for b in () if shap_only else (1024, 4096, 16384):
         recs = make_request_batch(b, seed=b)
         codes, nums = encode_batch(recs, p.vocabs)
         d_nums = torch.from_numpy(nums).to(dev)
@@ -91,7 +93,7 @@ def main():
     if_off = torch.from_numpy(p.if_tree_offsets).to(dev)
     fc = torch.from_numpy(p.feat_col).to(dev)
     fk = torch.from_numpy(p.feat_code).to(dev)
-    for b in (1024, 16384):
+    for b in () if shap_only else (1024, 16384):
         recs = make_request_batch(b, seed=b)
         codes, nums = encode_batch(recs, p.vocabs)
         d_codes = torch.from_numpy(codes).to(dev)
@@ -121,7 +123,9 @@ def main():
     # attributions next to the scorer's classifier kernel at the same shape:
     # forest_contrib vs forest_kernel<false> (ilp=0, the kernel
     # score_forest_pipeline launches for the classifier), interleaved rounds
-    if p.cls_node_value is None:
+    if shap_only:
+        pass
+    elif p.cls_node_value is None:
         results["forest_contrib"] = "skipped: cached bench model predates node values"
     else:
         node_value = torch.from_numpy(p.cls_node_value).to(dev)
@@ -157,6 +161,63 @@ def main():
         results[f"forest_contrib/forest_cls b={b}"] = round(
             stats["forest_contrib"]["median_us"] / stats["forest_cls"]["median_us"], 3
         )
+
+    # exact TreeSHAP next to the Saabas kernel on the same model: the path
+    # table's size and build time, then forest_shap vs forest_contrib at a
+    # full request (1024 rows) and at one row, interleaved rounds
+    if p.cls_node_cover is None or p.cls_node_value is None:
+        results["forest_shap"] = "skipped: cached bench model predates node cover"
+    else:
+        import time
+
+        from creditcore.engine import _check_shap_paths
+        from creditcore.pack import build_shap_paths
+
+        t0 = time.perf_counter()
+        paths, _ = build_shap_paths(p)
+        t1 = time.perf_counter()
+        _check_shap_paths(paths)
+        t2 = time.perf_counter()
+        results["forest_shap table"] = {
+            "leaves": paths.n_leaves,
+            "splits": int(len(paths.splits)),
+            "mean_depth": round(len(paths.splits) / max(paths.n_leaves, 1), 2),
+            "bytes": int(paths.splits.nbytes + paths.leaf_off.nbytes + paths.leaf_value.nbytes),
+            "build_s": round(t1 - t0, 3),
+            "check_s": round(t2 - t1, 3),
+        }
+        leaf_value = torch.from_numpy(paths.leaf_value).to(dev)
+        leaf_off = torch.from_numpy(paths.leaf_off).to(dev)
+        splits = torch.from_numpy(paths.splits).to(dev)
+        node_value = torch.from_numpy(p.cls_node_value).to(dev)
+        for b in (1024, 1):
+            codes, nums = encode_batch(make_request_batch(b, seed=b + 7), p.vocabs)
+            d_codes = torch.from_numpy(codes).to(dev)
+            d_nums = torch.from_numpy(nums).to(dev)
+
+            def shap(block_target=None, d_codes=d_codes, d_nums=d_nums):
+                extra = () if block_target is None else (block_target,)
+                return lambda: ext.forest_shap(
+                    d_codes, d_nums, leaf_value, leaf_off, splits, medians,
+                    p.cls_kind, p.cls_n_trees, *extra,
+                )
+
+            stats = timed_samples(
+                {
+                    "forest_shap": shap(),
+                    **{f"forest_shap blocks={t}": shap(t) for t in (1024, 8192)},
+                    "forest_contrib": lambda d_codes=d_codes, d_nums=d_nums: ext.forest_contrib(
+                        d_codes, d_nums, cls_nodes, node_value, cls_off, fc, fk,
+                        medians, p.cls_kind,
+                    ),
+                },
+                rounds=5, iters=1, warmup=1,  # a launch is long; few suffice
+            )
+            for k, v in stats.items():
+                results[f"{k} b={b} samples"] = v
+            results[f"forest_shap/forest_contrib b={b}"] = round(
+                stats["forest_shap"]["median_us"] / stats["forest_contrib"]["median_us"], 1
+            )
 
     print(json.dumps(results, indent=2))
 

@@ -80,12 +80,62 @@ def _check_forest_tables(p: PackedModel) -> None:
         raise ValueError("packed classifier forest is malformed; refusing to explain")
 
 
+def _check_shap_paths(paths, n_players: int = N_CAT + N_NUM) -> None:
+    """Host-side bounds check of everything forest_shap_kernel indexes with
+    path-table data before the first upload: leaf offsets into the split
+    records, the player (source column) of every record, at most 23 player
+    groups per leaf (the kernel's LDS tables), and fractions in [0, 1]."""
+    from .pack import SHAP_CODE_SHIFT, SHAP_FIRST, SHAP_PLAYER_SHIFT
+
+    lv, off, sp = paths.leaf_value, paths.leaf_off, paths.splits
+    ok = (
+        lv.ndim == 1
+        and lv.dtype == np.float32
+        and off.dtype == np.int32
+        and off.shape == (len(lv) + 1,)
+        and sp.dtype == np.int32
+        and sp.ndim == 2
+        and sp.shape[1] == 4
+        and off[0] == 0
+        and off[-1] == len(sp)
+        and bool((np.diff(off) >= 0).all())
+        and bool(np.isfinite(lv).all())
+    )
+    if ok and len(sp):
+        flags = sp[:, 3].view(np.uint32).astype(np.int64)
+        player = (flags >> SHAP_PLAYER_SHIFT) & 0xFF
+        numeric = (flags >> SHAP_CODE_SHIFT) == 0
+        first = (flags & SHAP_FIRST) != 0
+        frac = sp[:, 2].view(np.float32)
+        starts = off[:-1][np.diff(off) > 0]
+        rec_leaf = np.repeat(np.arange(len(lv)), np.diff(off))
+        groups = np.bincount(rec_leaf[first], minlength=len(lv))
+        ok = (
+            bool((player < n_players).all())
+            and bool((player[numeric] >= N_CAT).all())
+            and bool((player[~numeric] < N_CAT).all())
+            and bool(first[starts].all())  # every leaf's run opens a group
+            and int(groups.max()) <= n_players
+            and bool(((frac >= 0.0) & (frac <= 1.0)).all())
+            and bool(np.isfinite(sp[:, 1].view(np.float32)).all())
+        )
+    if not ok:
+        raise ValueError("SHAP path table is malformed; refusing to explain")
+
+
+EXPLAIN_METHODS = ("saabas", "shap")
+
+
 class ScoringEngine:
     # K-S kernel LDS sort capacity (csrc MAX_DRIFT_ROWS) — the hardware
     # ceiling; the per-engine cap (config drift_max_batch) can only lower it
     HW_DRIFT_MAX_ROWS = 16384
     # per-call row cap of explain_arrays / explain_records / POST /explain
     EXPLAIN_MAX_ROWS = 16384
+    # per-call row cap of method="shap": the cost is rows x leaves of the
+    # forest (every path, not one per tree), and one launch has to stay
+    # short on a shared GPU
+    SHAP_MAX_ROWS = 1024
 
     def __init__(
         self,
@@ -104,6 +154,8 @@ class ScoringEngine:
         self._gpu = None
         self._explain_lock = threading.Lock()
         self._explain_dev = None  # lazily uploaded device tensors (explain)
+        self._shap = None  # lazily built (paths, base value) of method="shap"
+        self._shap_dev = None  # lazily uploaded path table
         if device == "cuda":
             self._init_gpu()
 
@@ -199,8 +251,14 @@ class ScoringEngine:
         return out
 
     # ------------------------------------------------------- attributions
-    def explain_arrays(self, codes: np.ndarray, nums: np.ndarray) -> dict:
-        """Per-row prediction-path (Saabas) attributions for the classifier.
+    def explain_arrays(
+        self, codes: np.ndarray, nums: np.ndarray, method: str = "saabas"
+    ) -> dict:
+        """Per-row attributions for the classifier: prediction-path (Saabas)
+        contributions by default, exact path-dependent TreeSHAP values with
+        ``method="shap"`` (same keys; ``base_value`` is then the SHAP base,
+        the cover-weighted expectation of the model output, and the call is
+        capped at SHAP_MAX_ROWS).
 
         Returns ``contributions`` f64[B, 23] in schema.FEATURES order,
         ``base_value``, ``output_space`` ("probability" for the averaging
@@ -209,6 +267,12 @@ class ScoringEngine:
         kernels are not run. base_value + contributions.sum(1) is the model
         output by construction."""
         p = self.packed
+        if method not in EXPLAIN_METHODS:
+            raise ValueError(
+                f"unknown explain method {method!r}; expected one of {EXPLAIN_METHODS}"
+            )
+        if method == "shap":
+            return self._explain_shap(codes, nums)
         if p.cls_node_value is None:
             raise ExplainUnavailable(
                 "model was packed without per-node expected values; "
@@ -288,10 +352,80 @@ class ScoringEngine:
                 )
                 return out.cpu().numpy()  # D2H copy synchronizes the stream
 
-    def explain_records(self, records) -> dict:
+    def _explain_shap(self, codes: np.ndarray, nums: np.ndarray) -> dict:
+        p = self.packed
+        if p.cls_node_cover is None:
+            raise ExplainUnavailable(
+                "model was packed without per-node cover; re-pack it from "
+                "the trained pipeline to enable SHAP attributions"
+            )
+        b = len(codes)
+        if b > self.SHAP_MAX_ROWS:
+            raise ExplainTooLarge(
+                f"explain with method='shap' is capped at {self.SHAP_MAX_ROWS} "
+                f"rows per call (got {b})"
+            )
+        codes = np.ascontiguousarray(codes, dtype=np.int16).reshape(b, N_CAT)
+        nums = np.ascontiguousarray(nums, dtype=np.float32).reshape(b, N_NUM)
+        # The lock covers the lazy table build/upload and the call, as for
+        # the Saabas tensors; nothing here is shared with the scoring session.
+        with self._explain_lock:
+            if self._shap is None:
+                from .pack import build_shap_paths
+
+                paths, base = build_shap_paths(p)
+                _check_shap_paths(paths)
+                self._shap = (paths, base)
+            paths, base = self._shap
+            if self.device == "cuda":
+                contrib = self._shap_gpu(paths, codes, nums)
+            else:
+                contrib = cpu_ref.forest_shap_cpu(
+                    p, codes, cpu_ref.impute_nums(p, nums), paths=paths
+                )
+        raw = base + contrib.sum(axis=1)
+        log_odds = int(getattr(p, "cls_kind", 0)) == 1
+        return {
+            "contributions": contrib,
+            "base_value": base,
+            "output_space": "log_odds" if log_odds else "probability",
+            "predictions": 1.0 / (1.0 + np.exp(-raw)) if log_odds else raw,
+        }
+
+    def _shap_gpu(self, paths, codes: np.ndarray, nums: np.ndarray) -> np.ndarray:
+        """forest_shap on the device; the caller holds _explain_lock."""
+        import torch
+
+        ext = self._gpu["ext"]
+        dev = torch.device("cuda", self.device_index)
+        m = self._shap_dev
+        if m is None:
+            m = {
+                "leaf_value": torch.from_numpy(paths.leaf_value).to(dev),
+                "leaf_off": torch.from_numpy(paths.leaf_off).to(dev),
+                "splits": torch.from_numpy(np.ascontiguousarray(paths.splits)).to(dev),
+                "medians": torch.from_numpy(
+                    np.ascontiguousarray(self.packed.medians, dtype=np.float32)
+                ).to(dev),
+            }
+            self._shap_dev = m
+        with torch.cuda.device(dev):
+            out = ext.forest_shap(
+                torch.from_numpy(codes).to(dev),
+                torch.from_numpy(nums).to(dev),
+                m["leaf_value"],
+                m["leaf_off"],
+                m["splits"],
+                m["medians"],
+                int(getattr(self.packed, "cls_kind", 0)),
+                int(self.packed.cls_n_trees),
+            )
+            return out.cpu().numpy()  # D2H copy synchronizes the stream
+
+    def explain_records(self, records, method: str = "saabas") -> dict:
         """explain_arrays on a request body (list of dicts / DataFrame)."""
         codes, nums = encode_batch(records, self.packed.vocabs)
-        return self.explain_arrays(codes, nums)
+        return self.explain_arrays(codes, nums, method=method)
 
     def encode_json_body(self, body: bytes) -> tuple:
         """Parse a raw /score JSON body into (codes, nums) with the native C

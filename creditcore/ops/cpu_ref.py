@@ -139,6 +139,116 @@ def forest_contrib_cpu(
     return acc.reshape(n_rows, n_src) * scale
 
 
+# 12-point Gauss-Legendre rule on [0, 1]: exact for polynomials of degree
+# <= 23, and the SHAP integrand has degree (players on a path) - 1 <= 22.
+# The kernel carries the same nodes and weights as literals.
+SHAP_NQ = 12
+_gl_x, _gl_w = np.polynomial.legendre.leggauss(SHAP_NQ)
+SHAP_T = 0.5 * (_gl_x + 1.0)
+SHAP_W = 0.5 * _gl_w
+
+
+def forest_shap_cpu(
+    packed: PackedModel,
+    codes: np.ndarray,
+    nums_imp: np.ndarray,
+    paths=None,
+    max_bytes: int = 64 << 20,
+) -> np.ndarray:
+    """Exact path-dependent TreeSHAP values, f64[B, N_CAT + N_NUM] in schema
+    feature order (one-hot features fold onto their categorical column).
+
+    Per leaf with value v and distinct players p on its path (z_p = product
+    of cover fractions over p's splits, o_p = 1 iff the row follows them all):
+
+        phi_i = v * (o_i - z_i) * int_0^1 prod_{p != i} (z_p (1-t) + o_p t) dt
+
+    evaluated with the 12-point Gauss-Legendre rule (exact at this degree).
+    Same f32 compares as score_forest_cpu; everything else is f64. Scaled by
+    1/T for the averaging forests, 1 for gradient boosting, so that the SHAP
+    base value of pack.build_shap_paths plus the row sum is the model output.
+    ``paths`` takes a prebuilt table (the engine caches it). Leaves are
+    processed in chunks so that temporaries stay under ``max_bytes``."""
+    from ..pack import (
+        SHAP_CODE_SHIFT,
+        SHAP_DIR_RIGHT,
+        SHAP_FIRST,
+        SHAP_PLAYER_SHIFT,
+        build_shap_paths,
+    )
+
+    if paths is None:
+        paths, _ = build_shap_paths(packed)
+    n_rows = len(codes)
+    n_src = N_CAT + N_NUM
+    acc = np.zeros((n_rows, n_src), dtype=np.float64)
+    T = len(packed.cls_tree_offsets) - 1
+    scale = 1.0 if getattr(packed, "cls_kind", 0) == 1 else 1.0 / T
+    off = paths.leaf_off.astype(np.int64)
+    n_rec = int(off[-1])
+    if n_rows == 0 or n_rec == 0:
+        return acc
+
+    sp = paths.splits
+    thr = sp[:, 1].view(np.float32)
+    frac = sp[:, 2].view(np.float32).astype(np.float64)
+    flags = sp[:, 3].view(np.uint32).astype(np.int64)
+    right = (flags & SHAP_DIR_RIGHT) != 0
+    first = (flags & SHAP_FIRST) != 0
+    player = (flags >> SHAP_PLAYER_SHIFT) & 0xFF
+    code = (flags >> SHAP_CODE_SHIFT) - 1
+
+    # group = one player's run of records within one leaf
+    gstart = np.flatnonzero(first)
+    rec_leaf = np.repeat(np.arange(paths.n_leaves), np.diff(off))
+    leaf_goff = np.zeros(len(off), dtype=np.int64)  # first group of each leaf
+    np.cumsum(np.bincount(rec_leaf[gstart], minlength=paths.n_leaves), out=leaf_goff[1:])
+    z_all = np.multiply.reduceat(frac, gstart)
+    g_player = player[gstart]
+
+    codes = np.asarray(codes)
+    t = SHAP_T[None, None, :]
+    # per group: o, f, the leaf products and the quotient — ~4 x [B, G, NQ] f64
+    g_max = max(1, max_bytes // (4 * 8 * SHAP_NQ * n_rows))
+    n_leaves = paths.n_leaves
+    a = 0
+    while a < n_leaves:
+        b = int(np.searchsorted(leaf_goff, leaf_goff[a] + g_max, side="right")) - 1
+        b = min(max(b, a + 1), n_leaves)
+        g0, g1 = int(leaf_goff[a]), int(leaf_goff[b])
+        r0, r1 = int(off[a]), int(off[b])
+        if g1 == g0:
+            a = b
+            continue
+        # does the row follow each record? (f32 compare, as the scorer)
+        cat = code[r0:r1] >= 0
+        pl = player[r0:r1]
+        x = np.empty((n_rows, r1 - r0), dtype=np.float32)
+        x[:, cat] = codes[:, pl[cat]] == code[r0:r1][cat][None, :]
+        x[:, ~cat] = nums_imp[:, pl[~cat] - N_CAT]
+        follows = ~(x <= thr[None, r0:r1]) == right[None, r0:r1]
+        o = np.logical_and.reduceat(follows, gstart[g0:g1] - r0, axis=1)
+        o = o.astype(np.float64)
+        z = z_all[g0:g1][None, :]
+        f = z[:, :, None] * (1.0 - t) + o[:, :, None] * t  # [B, G, NQ]
+        # product over the groups of each leaf (non-empty leaves only)
+        lg = leaf_goff[a:b] - g0
+        ne = leaf_goff[a + 1 : b + 1] > leaf_goff[a:b]
+        prod = np.multiply.reduceat(f, lg[ne], axis=1)  # [B, leaves_ne, NQ]
+        n_g = (leaf_goff[a + 1 : b + 1] - leaf_goff[a:b])[ne]
+        prod_g = np.repeat(prod, n_g, axis=1)
+        v_g = np.repeat(paths.leaf_value[a:b][ne].astype(np.float64), n_g)
+        live = o != z  # o == z contributes exactly 0 (and may have f == 0)
+        np.copyto(f, 1.0, where=~live[:, :, None])
+        s = ((prod_g / f) * SHAP_W[None, None, :]).sum(axis=2)
+        phi = np.where(live, v_g[None, :] * (o - z) * s, 0.0)
+        gp = g_player[g0:g1]
+        for c in np.unique(gp):
+            acc[:, c] += phi[:, gp == c].sum(axis=1)
+        a = b
+    return acc * scale
+
+
 def score_iforest_cpu(
     packed: PackedModel, nums_imp: np.ndarray
 ) -> tuple[np.ndarray, np.ndarray]:

@@ -69,7 +69,8 @@ def _pack_sklearn_tree(
 ):
     """Repack one sklearn tree_ into BFS node-SoA [n,4] int32 (bits column
     stores f32 as raw bits). With ``with_values`` also return the per-node
-    expected value f32[n] in the same BFS order (see ``_node_values``)."""
+    expected value f32[n] (see ``_node_values``) and the per-node cover
+    f32[n] (``weighted_n_node_samples``), both in the same BFS order."""
     cl = tree.children_left
     cr = tree.children_right
     feat = tree.feature
@@ -113,7 +114,7 @@ def _pack_sklearn_tree(
     nodes[:, 1] = f32.view(np.int32)
     if with_values:
         w = np.asarray(tree.weighted_n_node_samples, dtype=np.float64)[order]
-        return nodes, _node_values(nodes, w)
+        return nodes, _node_values(nodes, w), w.astype(np.float32)
     return nodes
 
 
@@ -194,6 +195,9 @@ class PackedModel:
     # (RF/ET: mean of root values; GBT: cls_bias + sum of root values)
     cls_node_value: np.ndarray | None = None  # f32[n_nodes]
     cls_base_value: float = 0.0
+    # optional per-node cover (training weight that reached the node),
+    # index-aligned with cls_nodes: what exact TreeSHAP needs on top
+    cls_node_cover: np.ndarray | None = None  # f32[n_nodes]
 
     meta: dict = field(default_factory=dict)
 
@@ -215,6 +219,8 @@ class PackedModel:
         if self.cls_node_value is not None:
             extra["cls_node_value"] = self.cls_node_value
             extra["cls_base_value"] = self.cls_base_value
+        if self.cls_node_cover is not None:
+            extra["cls_node_cover"] = self.cls_node_cover
         np.savez_compressed(
             path,
             **extra,
@@ -276,6 +282,7 @@ class PackedModel:
             cls_base_value=(
                 float(z["cls_base_value"]) if "cls_base_value" in z else 0.0
             ),
+            cls_node_cover=z["cls_node_cover"] if "cls_node_cover" in z else None,
         )
 
 
@@ -305,7 +312,7 @@ def pack_classifier_pipeline(pipeline) -> dict:
         feat_col.append(col)
         feat_code.append(-1)
 
-    trees, values = [], []
+    trees, values, covers = [], [], []
     cls_kind, cls_bias = 0, 0.0
     if hasattr(clf, "loss_") or type(clf).__name__ == "GradientBoostingClassifier":
         cls_kind = 1
@@ -324,9 +331,10 @@ def pack_classifier_pipeline(pipeline) -> dict:
         for est in clf.estimators_[:, 0]:
             t = est.tree_
             leaf_raw = np.asarray(t.value, dtype=np.float64)[:, 0, 0] * lr
-            nd, nv = _pack_sklearn_tree(t, leaf_raw, with_values=True)
+            nd, nv, nc = _pack_sklearn_tree(t, leaf_raw, with_values=True)
             trees.append(nd)
             values.append(nv)
+            covers.append(nc)
     else:
         for est in clf.estimators_:
             t = est.tree_
@@ -335,9 +343,10 @@ def pack_classifier_pipeline(pipeline) -> dict:
             sums[sums == 0] = 1.0
             leaf_p1 = value[:, 0, 1] / sums  # fraction of class 1 (normalised
             # either way: sklearn >=1.4 already stores fractions)
-            nd, nv = _pack_sklearn_tree(t, leaf_p1, with_values=True)
+            nd, nv, nc = _pack_sklearn_tree(t, leaf_p1, with_values=True)
             trees.append(nd)
             values.append(nv)
+            covers.append(nc)
     nodes, offsets = _concat_trees(trees)
     roots = np.asarray([float(v[0]) for v in values], dtype=np.float64)
     if cls_kind == 1:
@@ -357,7 +366,155 @@ def pack_classifier_pipeline(pipeline) -> dict:
         "cls_bias": cls_bias,
         "cls_node_value": np.concatenate(values),
         "cls_base_value": base_value,
+        "cls_node_cover": np.concatenate(covers),
     }
+
+
+# ---------------------------------------------------------------------------
+# Exact TreeSHAP: flat root-to-leaf path table
+# ---------------------------------------------------------------------------
+
+# flags word of a split record
+SHAP_DIR_RIGHT = 1  # the path takes the right child (x > threshold)
+SHAP_FIRST = 2  # first record of its player within the leaf's run
+SHAP_PLAYER_SHIFT = 8  # bits 8..15: source column (schema.FEATURES index)
+SHAP_CODE_SHIFT = 16  # bits 16..31: one-hot code + 1; 0 => numeric split
+
+
+@dataclass
+class ShapPaths:
+    """Every root-to-leaf path of the classifier forest, flattened.
+
+    ``splits[leaf_off[l]:leaf_off[l+1]]`` are leaf l's split records, grouped
+    by player (source column, ascending; path order within a player). One
+    record is 16 B: {virtual feature, f32 threshold bits, f32 bits of
+    frac = cover[child taken] / cover[split node], flags}."""
+
+    leaf_value: np.ndarray  # f32[L]
+    leaf_off: np.ndarray  # i32[L+1]
+    splits: np.ndarray  # i32[S, 4]
+
+    @property
+    def n_leaves(self) -> int:
+        return len(self.leaf_value)
+
+
+def build_shap_paths(packed: "PackedModel") -> tuple[ShapPaths, float]:
+    """Path table for exact path-dependent TreeSHAP and the SHAP base value.
+
+    The base value is the cover-weighted expectation of the model output,
+    sum_leaves v * prod_path frac under the forest's scaling (1/T for the
+    averaging forests; 1 plus cls_bias for gradient boosting), in f64 over
+    the same f32 ``frac`` values the table stores. Vectorised over all nodes:
+    the only Python loops run over tree levels."""
+    if packed.cls_node_cover is None:
+        raise ValueError(
+            "model was packed without per-node cover (cls_node_cover is None); "
+            "re-pack it to compute SHAP values"
+        )
+    nodes = np.asarray(packed.cls_nodes)
+    off = np.asarray(packed.cls_tree_offsets, dtype=np.int64)
+    cover = np.asarray(packed.cls_node_cover, dtype=np.float64)
+    n = len(nodes)
+    if cover.shape != (n,):
+        raise ValueError("cls_node_cover is not aligned with cls_nodes")
+    if not np.isfinite(cover).all() or (cover < 0).any():
+        raise ValueError("cls_node_cover must be finite and non-negative")
+    feat_code = np.asarray(packed.feat_code, dtype=np.int64)
+    feat_col = np.asarray(packed.feat_col, dtype=np.int64)
+    if feat_code.max(initial=-1) + 1 > 0xFFFF:
+        raise ValueError("one-hot code does not fit the split record")
+
+    sizes = np.diff(off)
+    base = np.repeat(off[:-1], sizes)  # first node of the own tree
+    split = nodes[:, 0] >= 0
+    sidx = np.flatnonzero(split)
+    left = base[sidx] + nodes[sidx, 2]
+    right = base[sidx] + nodes[sidx, 3]
+
+    parent = np.full(n, -1, dtype=np.int64)
+    went_right = np.zeros(n, dtype=np.int64)
+    parent[left] = sidx
+    parent[right] = sidx
+    went_right[right] = 1
+    child = np.concatenate([left, right])
+    pc = cover[parent[child]]
+    frac = np.zeros(n, dtype=np.float32)
+    # a zero-cover split has zero-cover children: both get frac = 0
+    frac[child] = np.divide(
+        cover[child], pc, out=np.zeros(len(child)), where=pc > 0
+    ).astype(np.float32)
+
+    # depth and reach probability, level by level from the roots
+    depth = np.zeros(n, dtype=np.int64)
+    reach = np.ones(n, dtype=np.float64)
+    frontier = off[:-1]
+    while True:
+        frontier = frontier[split[frontier]]
+        if not len(frontier):
+            break
+        kids = np.concatenate(
+            [base[frontier] + nodes[frontier, 2], base[frontier] + nodes[frontier, 3]]
+        )
+        depth[kids] = depth[parent[kids]] + 1
+        reach[kids] = reach[parent[kids]] * np.float64(frac[kids])
+        frontier = kids
+
+    leaves = np.flatnonzero(~split)
+    leaf_value = nodes[leaves, 1].view(np.float32).copy()
+    d = depth[leaves]
+    leaf_off = np.zeros(len(leaves) + 1, dtype=np.int64)
+    np.cumsum(d, out=leaf_off[1:])
+    n_rec = int(leaf_off[-1])
+    if n_rec >= 2**31:
+        raise ValueError("path table exceeds int32 indexing")
+
+    # walk every leaf up to its root at once; slot = position along the path
+    rec_child = np.empty(n_rec, dtype=np.int64)
+    cur = leaves.copy()
+    lid = np.arange(len(leaves))
+    while len(cur):
+        up = depth[cur] > 0
+        cur, lid = cur[up], lid[up]
+        rec_child[leaf_off[lid] + depth[cur] - 1] = cur
+        cur = parent[cur]
+    rec_split = parent[rec_child]
+    feat = nodes[rec_split, 0].astype(np.int64)
+    code = feat_code[feat]
+    player = np.where(code >= 0, feat_col[feat], N_CAT + feat_col[feat])
+
+    # group each leaf's records by player; stable, so path order survives
+    rec_leaf = np.repeat(np.arange(len(leaves)), d)
+    order = np.argsort(rec_leaf * (N_CAT + N_NUM) + player, kind="stable")
+    rec_child, rec_split = rec_child[order], rec_split[order]
+    feat, code, player = feat[order], code[order], player[order]
+    first = np.ones(n_rec, dtype=bool)
+    if n_rec > 1:
+        first[1:] = (player[1:] != player[:-1]) | (rec_leaf[1:] != rec_leaf[:-1])
+
+    flags = (
+        went_right[rec_child] * SHAP_DIR_RIGHT
+        + first * SHAP_FIRST
+        + (player << SHAP_PLAYER_SHIFT)
+        + ((code + 1) << SHAP_CODE_SHIFT)
+    )
+    splits = np.empty((n_rec, 4), dtype=np.int32)
+    splits[:, 0] = feat
+    splits[:, 1] = nodes[rec_split, 1]
+    splits[:, 2] = frac[rec_child].view(np.int32)
+    splits[:, 3] = flags.astype(np.uint32).view(np.int32)
+
+    total = float((leaf_value.astype(np.float64) * reach[leaves]).sum())
+    if int(getattr(packed, "cls_kind", 0)) == 1:
+        base_value = float(packed.cls_bias) + total
+    else:
+        base_value = total / (len(off) - 1)
+    paths = ShapPaths(
+        leaf_value=leaf_value,
+        leaf_off=leaf_off.astype(np.int32),
+        splits=splits,
+    )
+    return paths, base_value
 
 
 def pack_isolation_forest(detector) -> dict:

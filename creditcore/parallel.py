@@ -90,6 +90,9 @@ def broadcast_packed(
         if meta["has_node_value"]:
             meta["node_value_shape"] = list(packed.cls_node_value.shape)
             meta["cls_base_value"] = float(packed.cls_base_value)
+        meta["has_node_cover"] = packed.cls_node_cover is not None
+        if meta["has_node_cover"]:
+            meta["node_cover_shape"] = list(packed.cls_node_cover.shape)
         obj = [meta]
     else:
         obj = [None]
@@ -133,6 +136,18 @@ def broadcast_packed(
         dist.broadcast(nv, src=src, group=group)
         cls_node_value = nv.cpu().numpy()
 
+    # optional per-node cover (SHAP), handled like the node values
+    cls_node_cover = None
+    if meta["has_node_cover"]:
+        if is_src:
+            nc = torch.from_numpy(
+                np.ascontiguousarray(packed.cls_node_cover.astype(np.float32, copy=False))
+            ).to(device)
+        else:
+            nc = torch.empty(meta["node_cover_shape"], dtype=torch.float32, device=device)
+        dist.broadcast(nc, src=src, group=group)
+        cls_node_cover = nc.cpu().numpy()
+
     if is_src:
         return packed
     kw = {name: tensors[name].cpu().numpy() for name, _ in _ARRAY_FIELDS}
@@ -143,6 +158,7 @@ def broadcast_packed(
         lin_weight=lin_weight,
         cls_node_value=cls_node_value,
         cls_base_value=meta.get("cls_base_value", 0.0),
+        cls_node_cover=cls_node_cover,
         meta=meta["meta"],
         **kw,
     )

@@ -130,9 +130,11 @@ class Reason(BaseModel):
 
 
 class ExplainOutput(BaseModel):
-    """POST /explain response: per-row prediction-path (Saabas) attributions.
+    """POST /explain response: per-row attributions, prediction-path (Saabas)
+    by default or exact TreeSHAP values with ``?method=shap``.
     base_value + sum(contributions[r]) is the model output for row r in
-    ``output_space`` ("probability", or "log_odds" for gradient boosting)."""
+    ``output_space`` ("probability", or "log_odds" for gradient boosting).
+    ``method`` echoes the query parameter and is absent when none was given."""
 
     output_space: str
     base_value: float
@@ -140,6 +142,7 @@ class ExplainOutput(BaseModel):
     predictions: list[float]
     contributions: list[list[float]]
     top_reasons: list[list[Reason]]
+    method: str | None = None
 
 
 # The one-record CI smoke-test fixture (reference app/sample-request.json).

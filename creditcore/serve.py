@@ -28,7 +28,7 @@ from fastapi import FastAPI, HTTPException, Query, Request, Response
 
 from .config import ServeConfig
 from .batching import MicroBatcher
-from .engine import ExplainUnavailable, ScoringEngine, load_engine
+from .engine import EXPLAIN_METHODS, ExplainUnavailable, ScoringEngine, load_engine
 from .pack import encode_batch
 from .schema import FEATURES, ExplainOutput, LoanApplicant, ModelOutput
 from .utils import logging as reqlog
@@ -515,12 +515,21 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
     async def explain(
         request: Request,
         top_k: int = Query(3, ge=0, le=len(FEATURES)),
+        method: str | None = Query(None),
     ):
         """Per-row feature attributions ("reason codes") for the classifier:
-        prediction-path (Saabas) contributions per input feature, plus the
-        up-to-top_k features pushing each row toward default. One attempt on
-        one live replica; bypasses the micro-batcher."""
+        prediction-path (Saabas) contributions per input feature by default,
+        exact TreeSHAP values with ``?method=shap``, plus the up-to-top_k
+        features pushing each row toward default. One attempt on one live
+        replica; bypasses the micro-batcher."""
         import asyncio
+
+        if method is not None and method not in EXPLAIN_METHODS:
+            raise HTTPException(
+                status_code=422,
+                detail=f"method must be one of {list(EXPLAIN_METHODS)}",
+            )
+        use = method or "saabas"
 
         metrics: Metrics = state["metrics"]
         engines = state["engines"]
@@ -533,12 +542,21 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
             raise HTTPException(status_code=422, detail=f"bad record: {e}")
         if len(codes) == 0:
             raise HTTPException(status_code=400, detail="empty request batch")
-        if len(codes) > ScoringEngine.EXPLAIN_MAX_ROWS:
+        max_rows = (
+            ScoringEngine.SHAP_MAX_ROWS if use == "shap" else ScoringEngine.EXPLAIN_MAX_ROWS
+        )
+        if len(codes) > max_rows:
             raise HTTPException(
                 status_code=413,
-                detail=f"/explain takes at most {ScoringEngine.EXPLAIN_MAX_ROWS} rows",
+                detail=f"/explain (method={use}) takes at most {max_rows} rows",
             )
-        if engines[0].packed.cls_node_value is None:
+        if use == "shap" and engines[0].packed.cls_node_cover is None:
+            raise HTTPException(
+                status_code=501,
+                detail="the served model was packed without per-node cover; "
+                "re-pack it to enable /explain?method=shap",
+            )
+        if use == "saabas" and engines[0].packed.cls_node_value is None:
             raise HTTPException(
                 status_code=501,
                 detail="the served model was packed without per-node expected "
@@ -552,7 +570,7 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
         t0 = time.perf_counter()
         try:
             out = await asyncio.get_running_loop().run_in_executor(
-                None, engines[idx].explain_arrays, codes, nums
+                None, engines[idx].explain_arrays, codes, nums, use
             )
             pool.report_ok(idx)
         except ExplainUnavailable as e:
@@ -570,6 +588,8 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
             "contributions": contrib.tolist(),
             "top_reasons": top_reasons(contrib, top_k),
         }
+        if method is not None:  # a default request keeps its key set
+            payload["method"] = method
         metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
         return _json_response(payload)
 

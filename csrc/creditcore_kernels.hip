@@ -379,6 +379,175 @@ __global__ __launch_bounds__(CONTRIB_BLOCK) void forest_contrib_kernel(
   }
 }
 
+// Exact path-dependent TreeSHAP over the flat path table of pack.py
+// (build_shap_paths). For one leaf with value v and distinct players p on its
+// path (z_p = product of cover fractions over p's splits, o_p = 1 iff the row
+// follows all of them):
+//
+//   phi_i = v (o_i - z_i) * int_0^1 prod_{p != i} (z_p (1-t) + o_p t) dt
+//
+// The integrand has degree <= N_SRC - 2, so the SHAP_NQ-point Gauss-Legendre
+// rule is exact. With f_pq = z_p + (o_p - z_p) t_q and L_q = prod_p f_pq,
+// player i gets v (o_i - z_i) sum_q w_q L_q / f_iq:
+//   o_i = 0: f_iq = z_i (1 - t_q), z_i cancels: phi_i = -v sum_q w_q/(1-t_q) L_q
+//            (the same sum for every such player of the leaf; no division);
+//   o_i = 1: 1/f_iq depends on the path only, not on the row. The block
+//            computes those reciprocals once per path into LDS (one division
+//            per thread) and every row multiplies.
+//
+// forest_contrib_kernel's skeleton: one thread per row, CONTRIB_BLOCK rows
+// staged column-major in LDS with fused imputation, N_SRC f64 accumulators
+// per thread in LDS, blockIdx.y strides over paths. All threads of a block
+// work on the same path, so record loads are block-uniform and every loop has
+// a uniform trip count (the barriers below rely on that: threads past n_rows
+// stay in the loops on a clamped row and only skip the flush).
+// LDS: 33,024 B as forest_contrib_kernel + 2,208 B reciprocals + 464 B.
+#define SHAP_NQ 12
+static_assert(2 * SHAP_NQ >= N_SRC, "Gauss-Legendre rule too small for N_SRC players");
+
+#define SHAP_DIR_RIGHT 1
+#define SHAP_FIRST 2
+#define SHAP_PLAYER_SHIFT 8
+#define SHAP_CODE_SHIFT 16
+
+// Gauss-Legendre nodes t_q and weights w_q on [0, 1], and w_q / (1 - t_q)
+#define SHAP_T_LIST                                                         \
+  0.009219682876640378, 0.0479413718147626, 0.11504866290284765,            \
+  0.20634102285669126, 0.31608425050090994, 0.43738329574426554,            \
+  0.5626167042557344, 0.6839157494990901, 0.7936589771433087,               \
+  0.8849513370971523, 0.9520586281852375, 0.9907803171233596
+#define SHAP_W_LIST                                                         \
+  0.02358766819325601, 0.05346966299765944, 0.08003916427167306,            \
+  0.10158371336153282, 0.11674626826917732, 0.12457352290670134,            \
+  0.12457352290670134, 0.11674626826917732, 0.10158371336153282,            \
+  0.08003916427167306, 0.05346966299765944, 0.02358766819325601
+
+__global__ __launch_bounds__(CONTRIB_BLOCK) void forest_shap_kernel(
+    const short* __restrict__ codes,       // [B, N_CAT]
+    const float* __restrict__ nums,        // [B, N_NUM]
+    const float* __restrict__ medians,     // [N_NUM]
+    const float* __restrict__ leaf_value,  // [L]
+    const int* __restrict__ leaf_off,      // [L+1] into splits
+    const int4* __restrict__ splits,       // [S] {feat, thr bits, frac bits, flags}
+    int n_leaves,
+    int n_rows,
+    double scale,                          // 1/T (averaging forest) or 1 (GBT)
+    double* __restrict__ shap)             // [B, N_SRC], pre-zeroed
+{
+  constexpr double T[SHAP_NQ] = {SHAP_T_LIST};
+  constexpr double W[SHAP_NQ] = {SHAP_W_LIST};
+
+  __shared__ double s_acc[N_SRC * CONTRIB_BLOCK];
+  __shared__ short s_codes[N_CAT * CONTRIB_BLOCK];
+  __shared__ float s_nums[N_NUM * CONTRIB_BLOCK];
+  __shared__ double s_rcp[N_SRC * SHAP_NQ];  // 1 / f_pq for o_p = 1
+  // z_p per player group of the path. Two buffers by path parity: pass 2 of
+  // one path reads it while thread 0 may already write the next path's.
+  __shared__ double s_z[2][N_SRC];
+  __shared__ double s_t[SHAP_NQ];
+
+  const int tid = threadIdx.x;
+  const int row_raw = blockIdx.x * CONTRIB_BLOCK + tid;
+  const bool live = row_raw < n_rows;
+  const int row = live ? row_raw : n_rows - 1;  // n_rows >= 1 (host)
+
+#pragma unroll
+  for (int c = 0; c < N_CAT; ++c)
+    s_codes[c * CONTRIB_BLOCK + tid] = codes[(size_t)row * N_CAT + c];
+#pragma unroll
+  for (int c = 0; c < N_NUM; ++c) {
+    const float v = nums[(size_t)row * N_NUM + c];
+    s_nums[c * CONTRIB_BLOCK + tid] = isnan(v) ? medians[c] : v;
+  }
+#pragma unroll
+  for (int c = 0; c < N_SRC; ++c) s_acc[c * CONTRIB_BLOCK + tid] = 0.0;
+#pragma unroll
+  for (int q = 0; q < SHAP_NQ; ++q)
+    if (tid == q) s_t[q] = T[q];
+
+  int par = 0;
+  for (int leaf = blockIdx.y; leaf < n_leaves; leaf += gridDim.y) {
+    const int r0 = leaf_off[leaf];
+    const int r1 = leaf_off[leaf + 1];
+    if (r1 == r0) continue;  // root leaf: no players (block-uniform)
+    par ^= 1;
+    double* sz = s_z[par];
+
+    // pass 1: which player groups the row follows, z_p, and L_q
+    double L[SHAP_NQ];
+#pragma unroll
+    for (int q = 0; q < SHAP_NQ; ++q) L[q] = 1.0;
+    unsigned omask = 0;
+    int m = 0;  // player groups closed so far
+    double z = 1.0;
+    bool o = true;
+    for (int r = r0; r < r1; ++r) {
+      const int4 rec = splits[r];
+      const int player = (rec.w >> SHAP_PLAYER_SHIFT) & 0xFF;
+      const int code = (int)((unsigned)rec.w >> SHAP_CODE_SHIFT) - 1;
+      const float x =
+          (code >= 0) ? ((s_codes[player * CONTRIB_BLOCK + tid] == (short)code) ? 1.0f : 0.0f)
+                      : s_nums[(player - N_CAT) * CONTRIB_BLOCK + tid];
+      const bool right = !(x <= __int_as_float(rec.y));
+      o = o && (right == (bool)(rec.w & SHAP_DIR_RIGHT));
+      z *= (double)__int_as_float(rec.z);
+      const bool last = (r + 1 == r1) || (splits[r + 1].w & SHAP_FIRST);
+      if (last) {  // block-uniform
+        const double d = (o ? 1.0 : 0.0) - z;
+#pragma unroll
+        for (int q = 0; q < SHAP_NQ; ++q) L[q] *= fma(d, T[q], z);
+        omask |= (o ? 1u : 0u) << m;
+        if (tid == 0) sz[m] = z;
+        ++m;
+        z = 1.0;
+        o = true;
+      }
+    }
+
+    __syncthreads();  // sz complete; previous path's s_rcp reads are done
+    for (int j = tid; j < m * SHAP_NQ; j += CONTRIB_BLOCK) {
+      const double zp = sz[j / SHAP_NQ];
+      s_rcp[j] = 1.0 / fma(1.0 - zp, s_t[j % SHAP_NQ], zp);  // >= t_q > 0
+    }
+    __syncthreads();
+
+    // pass 2: credit every player of the path
+    const double v = (double)leaf_value[leaf];
+    double s0 = 0.0;
+#pragma unroll
+    for (int q = 0; q < SHAP_NQ; ++q) {
+      s0 = fma(W[q] / (1.0 - T[q]), L[q], s0);
+      L[q] *= W[q];
+    }
+    int p = 0;
+    for (int r = r0; r < r1; ++r) {
+      const int w = splits[r].w;
+      if (!(w & SHAP_FIRST)) continue;  // block-uniform
+      const int player = (w >> SHAP_PLAYER_SHIFT) & 0xFF;
+      const double zp = sz[p];
+      double phi;
+      if ((omask >> p) & 1u) {
+        double s = 0.0;
+#pragma unroll
+        for (int q = 0; q < SHAP_NQ; ++q) s = fma(L[q], s_rcp[p * SHAP_NQ + q], s);
+        phi = v * (1.0 - zp) * s;  // exactly 0 when z_p == 1
+      } else {
+        phi = (zp == 0.0) ? 0.0 : -v * s0;
+      }
+      s_acc[player * CONTRIB_BLOCK + tid] += phi;
+      ++p;
+    }
+  }
+
+  if (!live) return;
+  double* out = shap + (size_t)row * N_SRC;
+#pragma unroll
+  for (int c = 0; c < N_SRC; ++c) {
+    const double a = s_acc[c * CONTRIB_BLOCK + tid];
+    if (a != 0.0) atomicAdd(&out[c], a * scale);
+  }
+}
+
 // 4-tree ILP + optional transposed grid (blockIdx.x = tree chunk so the
 // dispatcher's id%8 XCD placement gives adjacent chunks to different XCDs,
 // keeping each XCD's L2 on a tree subset). Experimental A/B variants.
@@ -965,6 +1134,58 @@ torch::Tensor forest_contrib(
       contrib.data_ptr<double>());
   HIP_CHECK(hipGetLastError());
   return contrib;
+}
+
+// Exact TreeSHAP values f64[B, 23] for the classifier forest
+// (forest_shap_kernel) from the path table of pack.build_shap_paths.
+// Stateless like forest_contrib; the caller has bounds-checked the table.
+torch::Tensor forest_shap(
+    torch::Tensor codes, torch::Tensor nums,
+    torch::Tensor leaf_value, torch::Tensor leaf_off, torch::Tensor splits,
+    torch::Tensor medians, int64_t cls_kind, int64_t n_trees,
+    int64_t block_target)
+{
+  check_inputs(codes, nums);
+  TORCH_CHECK(block_target >= 1 && block_target <= 65535, "bad block_target");
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType st, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == codes.device(), name,
+                " must be on the inputs' GPU");
+    TORCH_CHECK(t.scalar_type() == st && t.is_contiguous(), name,
+                " has the wrong dtype or is not contiguous");
+  };
+  on_dev(nums, torch::kFloat32, "nums");
+  on_dev(leaf_value, torch::kFloat32, "leaf_value");
+  on_dev(leaf_off, torch::kInt32, "leaf_off");
+  on_dev(splits, torch::kInt32, "splits");
+  on_dev(medians, torch::kFloat32, "medians");
+  TORCH_CHECK(leaf_value.dim() == 1 && leaf_off.dim() == 1 &&
+              leaf_off.size(0) == leaf_value.size(0) + 1,
+              "leaf_off must have one entry more than leaf_value");
+  TORCH_CHECK(splits.dim() == 2 && splits.size(1) == 4, "splits must be [S, 4]");
+  TORCH_CHECK(medians.numel() == N_NUM, "medians must have N_NUM entries");
+  TORCH_CHECK(n_trees >= 1, "forest has no trees");
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)codes.get_device());
+  const int B = (int)codes.size(0);
+  const int L = (int)leaf_value.size(0);
+  auto shap = torch::zeros({B, N_SRC},
+      torch::TensorOptions().dtype(torch::kFloat64).device(codes.device()));
+  if (B == 0 || L == 0) return shap;
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  const int row_blocks = ceil_div(B, CONTRIB_BLOCK);
+  // As forest_contrib: enough path-chunks to fill the CUs at small B, few
+  // enough that the up-to-23 closing atomics per thread stay negligible.
+  const int chunks = std::max(1, std::min(ceil_div((int)block_target, row_blocks), L));
+  const double scale = (cls_kind == 1) ? 1.0 : 1.0 / (double)n_trees;
+  hipLaunchKernelGGL(forest_shap_kernel, dim3(row_blocks, chunks),
+      dim3(CONTRIB_BLOCK), 0, stream,
+      codes.data_ptr<short>(), nums.data_ptr<float>(), medians.data_ptr<float>(),
+      leaf_value.data_ptr<float>(), leaf_off.data_ptr<int>(),
+      reinterpret_cast<const int4*>(splits.data_ptr<int>()), L, B, scale,
+      shap.data_ptr<double>());
+  HIP_CHECK(hipGetLastError());
+  return shap;
 }
 
 torch::Tensor forest_ilp_bench(
@@ -2573,6 +2794,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cls_node_value"), py::arg("cls_off"), py::arg("feat_col"),
         py::arg("feat_code"), py::arg("medians"), py::arg("cls_kind"),
         py::arg("block_target") = 512);
+  m.def("forest_shap", &forest_shap,
+        "Per-row exact TreeSHAP feature attributions f64[B,23] (gfx950)",
+        py::arg("codes"), py::arg("nums"), py::arg("leaf_value"),
+        py::arg("leaf_off"), py::arg("splits"), py::arg("medians"),
+        py::arg("cls_kind"), py::arg("n_trees"),
+        py::arg("block_target") = 2048);
   m.def("drift_stats", &drift_stats,
         "Per-feature drift statistics: categorical histograms + K-S D (gfx950)");
   m.def("encode_records", &encode_records,
