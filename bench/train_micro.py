@@ -1,0 +1,115 @@
+"""Training micro-benchmark: HistGBTClassifier on the GPU vs sklearn.
+
+    python bench/train_micro.py --rows 20000
+    python bench/train_micro.py --rows 1000000 --skip-exact-gbt
+
+Every estimator gets the same preprocessed matrix (the pipeline's
+[one-hot | 14 numerics] feature space, dense f32), the same 80/20 split and
+the same n_estimators / max_depth / learning_rate. Prints one JSON line per
+estimator with the fit wall time (host binning and transfers included for
+hgbt) and the held-out log-loss, then one summary line. sklearn's exact
+GradientBoostingClassifier is single-threaded; --skip-exact-gbt leaves it out
+at row counts where it would run for many minutes.
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _matrix(n_rows: int, seed: int):
+    from creditcore.data import make_uci_shaped_frame
+    from creditcore.models.forest import make_classifier_pipeline
+    from creditcore.schema import FEATURES, TARGET
+
+    df = make_uci_shaped_frame(n_rows=n_rows, seed=seed)
+    pre = make_classifier_pipeline({}, "rf").named_steps["preprocessor"]
+    x = pre.fit_transform(df[FEATURES])
+    if hasattr(x, "toarray"):
+        x = x.toarray()
+    return np.ascontiguousarray(x, dtype=np.float32), df[TARGET].to_numpy().ravel()
+
+
+def _log_loss(y, p) -> float:
+    p = np.clip(p, 1e-15, 1 - 1e-15)
+    return float(-np.mean(y * np.log(p) + (1 - y) * np.log(1 - p)))
+
+
+def main(argv=None) -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=20_000)
+    ap.add_argument("--trees", type=int, default=100)
+    ap.add_argument("--depth", type=int, default=6)
+    ap.add_argument("--learning-rate", type=float, default=0.1)
+    ap.add_argument("--seed", type=int, default=2024)
+    ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
+    ap.add_argument("--repeats", type=int, default=2,
+                    help="hgbt fits; the first also pays one-time GPU start-up")
+    ap.add_argument("--skip-exact-gbt", action="store_true")
+    a = ap.parse_args(argv)
+
+    from sklearn.model_selection import train_test_split
+
+    from creditcore.models.hgbt import HistGBTClassifier
+
+    t0 = time.perf_counter()
+    x, y = _matrix(a.rows, a.seed)
+    xtr, xte, ytr, yte = train_test_split(x, y, test_size=0.2, random_state=a.seed)
+    shape = {"rows": a.rows, "train_rows": len(xtr), "features": x.shape[1],
+             "trees": a.trees, "depth": a.depth, "learning_rate": a.learning_rate}
+    print(json.dumps({"event": "data", **shape,
+                      "prep_s": round(time.perf_counter() - t0, 3)}), flush=True)
+
+    common = {"n_estimators": a.trees, "max_depth": a.depth,
+              "learning_rate": a.learning_rate}
+    results = {}
+
+    def run(name, make, repeats=1):
+        fits = []
+        for _ in range(repeats):
+            est = make()
+            t = time.perf_counter()
+            est.fit(xtr, ytr)
+            fits.append(time.perf_counter() - t)
+        rec = {"estimator": name, "fit_s": round(min(fits), 4),
+               "fit_s_all": [round(f, 4) for f in fits],
+               "log_loss": round(_log_loss(yte, est.predict_proba(xte)[:, 1]), 6)}
+        results[name] = rec
+        print(json.dumps(rec), flush=True)
+
+    run(f"hgbt[{a.device}]",
+        lambda: HistGBTClassifier(**common, device=a.device), repeats=a.repeats)
+    try:
+        from sklearn.ensemble import HistGradientBoostingClassifier
+    except ImportError:
+        print(json.dumps({"estimator": "sklearn_hist_gbt", "skipped": "not importable"}))
+    else:
+        run("sklearn_hist_gbt", lambda: HistGradientBoostingClassifier(
+            max_iter=a.trees, max_depth=a.depth, learning_rate=a.learning_rate,
+            max_leaf_nodes=None, early_stopping=False, random_state=a.seed))
+    if a.skip_exact_gbt:
+        print(json.dumps({"estimator": "sklearn_gbt", "skipped": "--skip-exact-gbt"}))
+    else:
+        from sklearn.ensemble import GradientBoostingClassifier
+
+        run("sklearn_gbt", lambda: GradientBoostingClassifier(**common, random_state=a.seed))
+
+    ours = results[f"hgbt[{a.device}]"]["fit_s"]
+    print(json.dumps({
+        "event": "summary", **shape,
+        **{f"{k}_fit_s": v["fit_s"] for k, v in results.items()},
+        **{f"speedup_vs_{k}": round(v["fit_s"] / ours, 2)
+           for k, v in results.items() if not k.startswith("hgbt")},
+    }), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -8,7 +8,8 @@ Reproduces the reference's sklearn pipeline exactly
 - estimator:   RandomForestClassifier(n_estimators, max_depth, criterion,
                n_jobs=-1)
 
-Training happens on CPU with sklearn (like the reference); *scoring* happens
+Training happens on CPU with sklearn (like the reference), except for the
+"hgbt" family, which trains on the GPU (models/hgbt.py); *scoring* happens
 on MI355X via the packed flat-buffer representation (creditcore.pack) and the
 HIP forest-traversal kernel (csrc/creditcore_kernels.hip (forest_kernel_ilpN)). This module is the
 golden CPU path the GPU path is tested against.
@@ -32,7 +33,10 @@ def make_classifier_pipeline(params: dict, algorithm: str = "rf") -> Pipeline:
     ...). ``algorithm``: "rf" (the reference's RandomForest), "gbt"
     (GradientBoostingClassifier — the north star's "gradient-boosted-tree
     traversal" family; same packed node-SoA format, scored by the same HIP
-    kernel with a sigmoid(sum + prior) finalize), or "et"
+    kernel with a sigmoid(sum + prior) finalize), "hgbt"
+    (models.hgbt.HistGBTClassifier — histogram gradient boosting trained by
+    HIP kernels on the GPU, packed and scored like "gbt"; ``params`` may
+    carry ``device`` for the training device), or "et"
     (ExtraTreesClassifier — identical tree structure and leaf-fraction-mean
     semantics to RF, so it rides the RF pack/score path unchanged).
     """
@@ -43,6 +47,15 @@ def make_classifier_pipeline(params: dict, algorithm: str = "rf") -> Pipeline:
         params.pop("criterion", None)  # rf-only knob from the search space
         params.setdefault("n_estimators", 200)
         estimator = GradientBoostingClassifier(**params)
+    elif algorithm == "hgbt":
+        from .hgbt import MAX_DEPTH, HistGBTClassifier
+
+        params = dict(params)
+        params.pop("criterion", None)  # rf-only knob from the search space
+        params.setdefault("n_estimators", 200)
+        if "max_depth" in params:  # the search space draws up to 24
+            params["max_depth"] = min(int(params["max_depth"]), MAX_DEPTH)
+        estimator = HistGBTClassifier(**params)
     elif algorithm == "et":
         from sklearn.ensemble import ExtraTreesClassifier
 

@@ -350,3 +350,122 @@ def score_batch_cpu(packed: PackedModel, codes: np.ndarray, nums: np.ndarray) ->
         "instance_score": iscore,
         "p_vals": pvals,
     }
+
+
+# ---------------------------------------------------------------------------
+# Histogram gradient-boosted-tree trainer: the three level primitives
+# (golden reference of hgbt_hist / hgbt_split / hgbt_route in
+# csrc/creditcore_kernels.hip; all results are integers or the same f64
+# formula, so the kernels are tested against these with exact equality)
+# ---------------------------------------------------------------------------
+
+HGBT_SHIFT = 20  # fractional bits of the int32 fixed-point gradients
+HGBT_REC = 9  # split record: gain bits, feat, bin, GL, HL, CL, G, H, C
+
+
+def hgbt_hist_cpu(
+    bins: np.ndarray,
+    bin_off: np.ndarray,
+    node: np.ndarray,
+    gq: np.ndarray,
+    hq: np.ndarray,
+    n_nodes: int,
+) -> np.ndarray:
+    """Level histogram i64[n_nodes, 3, total_bins]: per (open node, bin) the
+    sums of gq and hq and the row count. ``bins`` is u8[F, N] (feature-major),
+    ``node`` the per-row slot among the level's open nodes; rows with a
+    negative node id already sit in a leaf and are skipped.
+
+    bincount sums in f64, which is exact here: every partial sum is an
+    integer below 2^53 (N * 2^HGBT_SHIFT with N < 2^33)."""
+    n_feat = bins.shape[0]
+    total = int(bin_off[-1])
+    hist = np.zeros((n_nodes, 3, total), dtype=np.int64)
+    live = np.flatnonzero((node >= 0) & (node < n_nodes))
+    if not len(live):
+        return hist
+    nd = node[live].astype(np.int64)
+    g = gq[live].astype(np.float64)
+    h = hq[live].astype(np.float64)
+    for f in range(n_feat):
+        a, b = int(bin_off[f]), int(bin_off[f + 1])
+        nb = b - a
+        idx = nd * nb + bins[f, live].astype(np.int64)
+        size = n_nodes * nb
+        hist[:, 0, a:b] = np.bincount(idx, weights=g, minlength=size).astype(
+            np.int64
+        ).reshape(n_nodes, nb)
+        hist[:, 1, a:b] = np.bincount(idx, weights=h, minlength=size).astype(
+            np.int64
+        ).reshape(n_nodes, nb)
+        hist[:, 2, a:b] = np.bincount(idx, minlength=size).reshape(n_nodes, nb)
+    return hist
+
+
+def hgbt_split_cpu(
+    hist: np.ndarray, bin_off: np.ndarray, lam: float, min_leaf: int
+) -> np.ndarray:
+    """Best split per open node, i64[n_nodes, HGBT_REC].
+
+    For every (feature, bin b) the candidate "bin <= b goes left" has
+    gain = GL^2/(HL+lam) + GR^2/(HR+lam) - G^2/(H+lam), in f64 from the
+    integer prefix sums scaled by 2^-HGBT_SHIFT (exact). It is valid when both
+    sides keep ``min_leaf`` rows and gain > 0. Ties: highest gain, then lowest
+    feature, then lowest bin. No valid split: feat = -1 and zeros. The kernel
+    evaluates the same expression in the same order with contraction off."""
+    n_nodes, _, total = hist.shape
+    bin_off = np.asarray(bin_off, dtype=np.int64)
+    out = np.zeros((n_nodes, HGBT_REC), dtype=np.int64)
+    if n_nodes == 0:
+        return out
+    feat_of_bin = np.repeat(np.arange(len(bin_off) - 1), np.diff(bin_off))
+    start = bin_off[:-1][feat_of_bin]  # first bin of the own feature
+    cs = np.cumsum(hist, axis=2)
+    # prefix within the feature = running sum minus the sum before its start
+    before = np.where(start > 0, cs[:, :, np.maximum(start - 1, 0)], 0)
+    pre = cs - before  # [n_nodes, 3, total]
+    f0_last = int(bin_off[1]) - 1
+    tot = pre[:, :, f0_last]  # node totals (feature 0 sees every open row)
+    GL, HL, CL = pre[:, 0], pre[:, 1], pre[:, 2]
+    G, H, C = tot[:, 0:1], tot[:, 1:2], tot[:, 2:3]
+    sc = 1.0 / float(1 << HGBT_SHIFT)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        gl, hl = GL.astype(np.float64) * sc, HL.astype(np.float64) * sc
+        gr, hr = (G - GL).astype(np.float64) * sc, (H - HL).astype(np.float64) * sc
+        g, h = G.astype(np.float64) * sc, H.astype(np.float64) * sc
+        a = (gl * gl) / (hl + lam)
+        b = (gr * gr) / (hr + lam)
+        c = (g * g) / (h + lam)
+        gain = (a + b) - c
+        valid = (CL >= min_leaf) & (C - CL >= min_leaf) & (gain > 0.0)
+    gain = np.where(valid, gain, -np.inf)
+    # argmax returns the first maximum: lowest (feature, bin) among ties
+    best = np.argmax(gain, axis=1)
+    k = np.arange(n_nodes)
+    ok = valid[k, best]
+    out[:, 0] = np.where(ok, gain[k, best], 0.0).view(np.int64)
+    out[:, 1] = np.where(ok, feat_of_bin[best], -1)
+    out[:, 2] = np.where(ok, best - start[best], 0)
+    out[:, 3] = np.where(ok, GL[k, best], 0)
+    out[:, 4] = np.where(ok, HL[k, best], 0)
+    out[:, 5] = np.where(ok, CL[k, best], 0)
+    out[:, 6:9] = tot
+    return out
+
+
+def hgbt_route_cpu(bins: np.ndarray, table: np.ndarray, node: np.ndarray) -> np.ndarray:
+    """New per-row node ids. ``table[k] = {feat, bin, left, right}`` for open
+    node k: rows with bins[feat] <= bin take ``left``, the others ``right``;
+    feat < 0 closes the node and every row takes ``left``. Targets >= 0 are
+    slots of the next level, negative ones encode leaf node t as -(t + 1).
+    Rows already in a leaf keep their id."""
+    out = node.copy()
+    live = np.flatnonzero((node >= 0) & (node < len(table)))
+    if not len(live):
+        return out
+    t = table[node[live]]
+    feat = t[:, 0]
+    b = bins[np.maximum(feat, 0), live].astype(np.int64)
+    go_left = (feat < 0) | (b <= t[:, 1])
+    out[live] = np.where(go_left, t[:, 2], t[:, 3]).astype(node.dtype)
+    return out

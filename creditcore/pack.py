@@ -71,10 +71,30 @@ def _pack_sklearn_tree(
     stores f32 as raw bits). With ``with_values`` also return the per-node
     expected value f32[n] (see ``_node_values``) and the per-node cover
     f32[n] (``weighted_n_node_samples``), both in the same BFS order."""
-    cl = tree.children_left
-    cr = tree.children_right
-    feat = tree.feature
-    thr = tree.threshold
+    return _pack_tree_arrays(
+        tree.children_left,
+        tree.children_right,
+        tree.feature,
+        tree.threshold,
+        leaf_values,
+        cover=tree.weighted_n_node_samples if with_values else None,
+        feature_remap=feature_remap,
+    )
+
+
+def _pack_tree_arrays(
+    cl: np.ndarray,
+    cr: np.ndarray,
+    feat: np.ndarray,
+    thr: np.ndarray,
+    leaf_values: np.ndarray,
+    cover: np.ndarray | None = None,
+    feature_remap: np.ndarray | None = None,
+):
+    """BFS node-SoA of one tree given as plain flat arrays in sklearn's
+    ``tree_`` convention (leaf: children == -1; node 0 is the root). With
+    ``cover`` (per-node training weight) also return the per-node expected
+    value and the cover as f32, both in BFS order."""
     n = len(cl)
 
     order = np.empty(n, dtype=np.int64)
@@ -112,8 +132,8 @@ def _pack_sklearn_tree(
             nodes[k, 2] = int(new_idx[cl[i]])
             nodes[k, 3] = int(new_idx[cr[i]])
     nodes[:, 1] = f32.view(np.int32)
-    if with_values:
-        w = np.asarray(tree.weighted_n_node_samples, dtype=np.float64)[order]
+    if cover is not None:
+        w = np.asarray(cover, dtype=np.float64)[order]
         return nodes, _node_values(nodes, w), w.astype(np.float32)
     return nodes
 
@@ -289,9 +309,10 @@ class PackedModel:
 def pack_classifier_pipeline(pipeline) -> dict:
     """Extract vocabularies, medians and the BFS node-SoA forest from the
     sklearn pipeline built by make_classifier_pipeline. Supports the
-    reference's RandomForestClassifier (leaf-fraction mean) and
+    reference's RandomForestClassifier (leaf-fraction mean),
     GradientBoostingClassifier (lr-scaled regression leaves summed into a
-    logit on top of the prior)."""
+    logit on top of the prior) and models.hgbt.HistGBTClassifier (the same
+    finalize, from the estimator's own flat arrays)."""
     pre = pipeline.named_steps["preprocessor"]
     clf = pipeline.named_steps["classifier"]
 
@@ -314,7 +335,21 @@ def pack_classifier_pipeline(pipeline) -> dict:
 
     trees, values, covers = [], [], []
     cls_kind, cls_bias = 0, 0.0
-    if hasattr(clf, "loss_") or type(clf).__name__ == "GradientBoostingClassifier":
+    if type(clf).__name__ == "HistGBTClassifier":
+        # models/hgbt.py: plain arrays, f32 thresholds that are exact for f32
+        # inputs, leaves already scaled by the learning rate, integer covers
+        cls_kind = 1
+        cls_bias = float(clf.init_raw_)
+        for i in range(clf.n_trees_):
+            t = clf.tree_arrays(i)
+            nd, nv, nc = _pack_tree_arrays(
+                t["children_left"], t["children_right"], t["feature"],
+                t["threshold"], t["value"], cover=t["cover"],
+            )
+            trees.append(nd)
+            values.append(nv)
+            covers.append(nc)
+    elif hasattr(clf, "loss_") or type(clf).__name__ == "GradientBoostingClassifier":
         cls_kind = 1
         lr = float(clf.learning_rate)
         # binary log-loss prior (raw score of the init estimator)

@@ -60,8 +60,26 @@ class EvalRun:
     pipeline: object = field(repr=False, default=None)
 
 
+def _family_params(params: dict, algorithm: str, train_device: str) -> dict:
+    """Map a draw from the reference search space onto the estimator family:
+    hgbt has no split criterion, caps max_depth and takes a training device."""
+    if algorithm != "hgbt":
+        return params
+    from .models.hgbt import MAX_DEPTH
+
+    out = {k: v for k, v in params.items() if k != "criterion"}
+    if "max_depth" in out:
+        out["max_depth"] = min(int(out["max_depth"]), MAX_DEPTH)
+    out["device"] = train_device
+    return out
+
+
 def _evaluate(
-    params: dict, df: pd.DataFrame, seed: int = 2024, algorithm: str = "rf"
+    params: dict,
+    df: pd.DataFrame,
+    seed: int = 2024,
+    algorithm: str = "rf",
+    train_device: str = "auto",
 ) -> EvalRun:
     """One hyperparameter evaluation (reference cell-7, minus the dead
     double-fits)."""
@@ -71,7 +89,8 @@ def _evaluate(
     x_train, y_train = df_train[FEATURES], df_train[TARGET]
     x_test, y_test = df_test[FEATURES], df_test[TARGET]
 
-    estimator = make_classifier_pipeline({**params, "random_state": seed}, algorithm)
+    fit_params = _family_params(params, algorithm, train_device)
+    estimator = make_classifier_pipeline({**fit_params, "random_state": seed}, algorithm)
     estimator.fit(x_train, y_train.values.ravel())
     y_pred = estimator.predict(x_test)
 
@@ -83,7 +102,7 @@ def _evaluate(
         "validation_precision_score": precision_score(y_test, y_pred, zero_division=0),
         "validation_recall_score": recall_score(y_test, y_pred),
     }
-    return EvalRun(uuid.uuid4().hex, dict(params), metrics, estimator)
+    return EvalRun(uuid.uuid4().hex, dict(fit_params), metrics, estimator)
 
 
 def train_model(
@@ -94,6 +113,7 @@ def train_model(
     runs_dir: str | None = None,
     n_rows: int = 20_000,
     algorithm: str = "rf",
+    train_device: str = "auto",
 ) -> EvalRun:
     """Hyperparameter search with a real TPE sampler (reference cell-8:
     hyperopt fmin(tpe.suggest, max_evals=10); hyperopt itself is
@@ -108,7 +128,9 @@ def train_model(
     t0 = time.time()
     for i in range(max_evals):
         params = sampler.suggest()
-        run = _evaluate(params, df, seed=seed, algorithm=algorithm)
+        run = _evaluate(
+            params, df, seed=seed, algorithm=algorithm, train_device=train_device
+        )
         # hyperopt minimizes; the notebook returns -roc_auc as the loss
         sampler.observe(params, -run.metrics["validation_roc_auc_score"])
         if runs_dir:
@@ -155,13 +177,17 @@ def train_and_register(
     register: bool = True,
     algorithm: str = "rf",
     min_roc_auc: float | None = None,
+    train_device: str = "auto",
 ) -> str:
     """The full train -> package -> register job (the reference's 2-task
     Databricks DAG, train_register_model.yml:10-39). Returns the model URI
     (or the model dir when register=False)."""
     if df is None:
         df = make_uci_shaped_frame(n_rows=n_rows, seed=seed)
-    best = train_model(df=df, max_evals=max_evals, seed=seed, algorithm=algorithm)
+    best = train_model(
+        df=df, max_evals=max_evals, seed=seed, algorithm=algorithm,
+        train_device=train_device,
+    )
     if min_roc_auc is not None:
         auc = best.metrics["validation_roc_auc_score"]
         if auc < min_roc_auc:

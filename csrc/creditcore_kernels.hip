@@ -1188,6 +1188,357 @@ torch::Tensor forest_shap(
   return shap;
 }
 
+// ---------------------------------------------------------------------------
+// Histogram gradient-boosted-tree trainer (creditcore/models/hgbt.py).
+//
+// One tree level = three launches: hgbt_hist_kernel (per-(node, bin) integer
+// sums of the fixed-point gradients), hgbt_split_kernel (best split per node)
+// and hgbt_route_kernel (rows move to their child). Gradients arrive as int32
+// fixed point with HGBT_SHIFT fractional bits, so every histogram sum is an
+// integer and the result does not depend on the order atomics land in; the
+// CPU reference (ops/cpu_ref.py hgbt_*_cpu) must match bit for bit.
+//
+// Layouts: bins u8[F, N] column-major (feature-major), ragged bin offsets
+// bin_off i32[F+1]; per-row node id i32[N] = slot of the row's node among
+// the level's open nodes, negative once the row sits in a leaf; histogram
+// i64[n_nodes, 3, total_bins] with planes {sum g, sum h, row count}.
+// ---------------------------------------------------------------------------
+
+#define HGBT_BLOCK 256
+#define HGBT_SHIFT 20
+#define HGBT_MAX_BINS 256
+#define HGBT_REC 9  // split record, i64 words: gain bits, feat, bin, GL, HL, CL, G, H, C
+// int32 LDS partials: |gq| <= 2^HGBT_SHIFT per row, so a block may sum at most
+// this many rows before a partial could leave int32.
+static constexpr int64_t HGBT_MAX_ROWS_PER_BLOCK = (int64_t(1) << (31 - HGBT_SHIFT)) - 1;
+static constexpr size_t HGBT_LDS_BYTES_MAX = 160 * 1024 - 1024;  // gfx950 LDS/CU
+
+// grid = (row blocks, feature groups). lds_entries > 0: the block's
+// (n_nodes x 3 x group bins) slab is summed in LDS with int32 atomics and
+// flushed with one global atomic per non-zero entry; lds_entries == 0 (deep
+// levels, slab larger than LDS): int64 atomics straight to global memory.
+// Every offset read from bin_off / grp_off is range-checked before use, so
+// bad table contents skip work instead of writing out of bounds.
+__global__ __launch_bounds__(HGBT_BLOCK) void hgbt_hist_kernel(
+    const uint8_t* __restrict__ bins, const int* __restrict__ bin_off,
+    const int* __restrict__ grp_off, const int* __restrict__ node,
+    const int* __restrict__ gq, const int* __restrict__ hq,
+    long long n_rows, int n_feat, int n_nodes, int total_bins,
+    int rows_per_block, int lds_entries,
+    unsigned long long* __restrict__ hist)
+{
+  extern __shared__ int hgbt_lds[];
+  const int tid = threadIdx.x;
+  const int f0 = grp_off[blockIdx.y], f1 = grp_off[blockIdx.y + 1];
+  if (f0 < 0 || f1 > n_feat || f0 >= f1) return;
+  const int b0 = bin_off[f0];
+  const int gb = bin_off[f1] - b0;  // bins of this feature group
+  if (b0 < 0 || gb <= 0 || (long long)b0 + gb > total_bins) return;
+  const bool use_lds = lds_entries > 0;
+  const long long slab = (long long)n_nodes * 3 * gb;
+  if (use_lds) {
+    if (slab > lds_entries) return;  // host sizes the allocation from the same tables
+    for (int i = tid; i < (int)slab; i += HGBT_BLOCK) hgbt_lds[i] = 0;
+    __syncthreads();
+  }
+
+  const long long r0 = (long long)blockIdx.x * rows_per_block;
+  const long long r1 = min(r0 + (long long)rows_per_block, n_rows);
+  // consecutive lanes take consecutive rows: the u8 column reads coalesce
+  for (long long r = r0 + tid; r < r1; r += HGBT_BLOCK) {
+    const int nd = node[r];
+    if (nd < 0 || nd >= n_nodes) continue;  // row already in a leaf
+    const int g = gq[r], h = hq[r];
+    for (int f = f0; f < f1; ++f) {
+      const int fb = bin_off[f];
+      const int nb = bin_off[f + 1] - fb;
+      if (fb < b0 || nb <= 0 || fb + nb > b0 + gb) continue;
+      const int b = bins[(size_t)f * (size_t)n_rows + (size_t)r];
+      if (b >= nb) continue;
+      if (use_lds) {
+        int* p = hgbt_lds + (size_t)nd * 3 * gb + (fb - b0) + b;
+        atomicAdd(p, g);
+        atomicAdd(p + gb, h);
+        atomicAdd(p + 2 * gb, 1);
+      } else {
+        unsigned long long* p = hist + (size_t)nd * 3 * total_bins + fb + b;
+        atomicAdd(p, (unsigned long long)(long long)g);
+        atomicAdd(p + total_bins, (unsigned long long)(long long)h);
+        atomicAdd(p + 2 * (size_t)total_bins, 1ull);
+      }
+    }
+  }
+
+  if (use_lds) {
+    __syncthreads();
+    for (int i = tid; i < (int)slab; i += HGBT_BLOCK) {
+      const int v = hgbt_lds[i];
+      if (v == 0) continue;
+      const int plane = i / gb;  // node * 3 + {g, h, count}
+      const int b = i - plane * gb;
+      atomicAdd(hist + (size_t)plane * total_bins + b0 + b,
+                (unsigned long long)(long long)v);
+    }
+  }
+}
+
+// Split gain from the integer sums, in f64. The operation order is the one
+// hgbt_split_cpu uses, and contraction is off: an FMA here would round
+// differently from numpy and break the bit-exact agreement.
+__device__ __forceinline__ double hgbt_gain(
+    long long GL, long long HL, long long G, long long H, double lam)
+{
+#pragma clang fp contract(off)
+  const double sc = 1.0 / (double)(1 << HGBT_SHIFT);
+  const double gl = (double)GL * sc, hl = (double)HL * sc;
+  const double gr = (double)(G - GL) * sc, hr = (double)(H - HL) * sc;
+  const double g = (double)G * sc, h = (double)H * sc;
+  const double a = (gl * gl) / (hl + lam);
+  const double b = (gr * gr) / (hr + lam);
+  const double c = (g * g) / (h + lam);
+  return (a + b) - c;
+}
+
+struct HgbtBest {
+  double gain;
+  int feat, bin;
+  long long GL, HL, CL;
+};
+
+// highest gain, then lowest feature, then lowest bin; feat < 0 = no split yet
+__device__ __forceinline__ bool hgbt_better(const HgbtBest& a, const HgbtBest& b) {
+  if (a.feat < 0) return false;
+  if (b.feat < 0) return true;
+  if (a.gain != b.gain) return a.gain > b.gain;
+  if (a.feat != b.feat) return a.feat < b.feat;
+  return a.bin < b.bin;
+}
+
+__device__ __forceinline__ HgbtBest hgbt_shfl_xor(const HgbtBest& v, int m) {
+  HgbtBest o;
+  o.gain = __shfl_xor(v.gain, m);
+  o.feat = __shfl_xor(v.feat, m);
+  o.bin = __shfl_xor(v.bin, m);
+  o.GL = __shfl_xor(v.GL, m);
+  o.HL = __shfl_xor(v.HL, m);
+  o.CL = __shfl_xor(v.CL, m);
+  return o;
+}
+
+// One block per open node; each of its 4 wavefronts takes every 4th feature.
+// A lane owns 4 consecutive bins (64 x 4 = HGBT_MAX_BINS), scans them, and a
+// wave-wide shuffle scan of the lane totals gives the prefix sums. "bin <= b
+// goes left" is valid when both sides keep min_leaf rows and the gain is > 0.
+__global__ __launch_bounds__(HGBT_BLOCK) void hgbt_split_kernel(
+    const long long* __restrict__ hist, const int* __restrict__ bin_off,
+    int n_feat, int total_bins, double lam, long long min_leaf,
+    long long* __restrict__ out)
+{
+  __shared__ HgbtBest wave_best[HGBT_BLOCK / 64];
+  __shared__ long long wave_tot[HGBT_BLOCK / 64][3];
+  const int k = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long* hg = hist + (size_t)k * 3 * total_bins;
+  const long long* hh = hg + total_bins;
+  const long long* hc = hh + total_bins;
+
+  HgbtBest best;
+  best.gain = 0.0; best.feat = -1; best.bin = 0; best.GL = best.HL = best.CL = 0;
+  long long G = 0, H = 0, C = 0;
+  for (int f = wave; f < n_feat; f += HGBT_BLOCK / 64) {
+    const int fb = bin_off[f];
+    const int nb = bin_off[f + 1] - fb;
+    if (fb < 0 || nb <= 0 || nb > HGBT_MAX_BINS || fb + nb > total_bins) continue;
+    long long pg[4], ph[4], pc[4];
+    long long sg = 0, sh = 0, sc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int b = lane * 4 + j;
+      if (b < nb) { sg += hg[fb + b]; sh += hh[fb + b]; sc += hc[fb + b]; }
+      pg[j] = sg; ph[j] = sh; pc[j] = sc;
+    }
+    // inclusive scan of the lane totals across the wavefront
+    long long ig = sg, ih = sh, ic = sc;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const long long tg = __shfl_up(ig, d), th = __shfl_up(ih, d), tc = __shfl_up(ic, d);
+      if (lane >= d) { ig += tg; ih += th; ic += tc; }
+    }
+    // every feature sees every open row once: the totals are the node's own
+    G = __shfl(ig, 63); H = __shfl(ih, 63); C = __shfl(ic, 63);
+    const long long og = ig - sg, oh = ih - sh, oc = ic - sc;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int b = lane * 4 + j;
+      if (b >= nb) continue;
+      const long long CL = oc + pc[j];
+      if (CL < min_leaf || C - CL < min_leaf) continue;
+      HgbtBest c;
+      c.GL = og + pg[j]; c.HL = oh + ph[j]; c.CL = CL;
+      c.feat = f; c.bin = b;
+      c.gain = hgbt_gain(c.GL, c.HL, G, H, lam);
+      if (!(c.gain > 0.0)) continue;
+      if (hgbt_better(c, best)) best = c;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const HgbtBest o = hgbt_shfl_xor(best, m);
+    if (hgbt_better(o, best)) best = o;
+  }
+  if (lane == 0) {
+    wave_best[wave] = best;
+    wave_tot[wave][0] = G; wave_tot[wave][1] = H; wave_tot[wave][2] = C;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < HGBT_BLOCK / 64; ++w)
+      if (hgbt_better(wave_best[w], best)) best = wave_best[w];
+    // wave 0 always scans feature 0 (n_feat >= 1), so its totals are set
+    long long* o = out + (size_t)k * HGBT_REC;
+    o[0] = __double_as_longlong(best.feat < 0 ? 0.0 : best.gain);
+    o[1] = best.feat; o[2] = best.bin;
+    o[3] = best.GL; o[4] = best.HL; o[5] = best.CL;
+    o[6] = wave_tot[0][0]; o[7] = wave_tot[0][1]; o[8] = wave_tot[0][2];
+  }
+}
+
+// table[k] = {feat, bin, left, right} for open node k: rows with
+// bins[feat] <= bin take `left`, the others `right`; feat < 0 closes the node
+// and every row takes `left`. A target >= 0 is the child's slot in the next
+// level, a negative one encodes leaf node t of the tree as -(t + 1).
+__global__ __launch_bounds__(HGBT_BLOCK) void hgbt_route_kernel(
+    const uint8_t* __restrict__ bins, const int4* __restrict__ table,
+    long long n_rows, int n_feat, int n_nodes, int* __restrict__ node)
+{
+  const long long r = (long long)blockIdx.x * HGBT_BLOCK + threadIdx.x;
+  if (r >= n_rows) return;
+  const int nd = node[r];
+  if (nd < 0 || nd >= n_nodes) return;
+  const int4 t = table[nd];
+  if (t.x < 0) {
+    node[r] = t.z;
+  } else if (t.x < n_feat) {
+    const int b = bins[(size_t)t.x * (size_t)n_rows + (size_t)r];
+    node[r] = (b <= t.y) ? t.z : t.w;
+  }
+}
+
+void hgbt_check(const torch::Tensor& t, const torch::Tensor& like,
+                torch::ScalarType st, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name,
+              " must be on the bin matrix's GPU");
+  TORCH_CHECK(t.scalar_type() == st && t.is_contiguous(), name,
+              " has the wrong dtype or is not contiguous");
+}
+
+// Level histogram i64[n_nodes, 3, total_bins]. lds_entries is the int32
+// entry count of the largest feature group's slab (n_nodes * 3 * group bins),
+// or 0 to take the direct-global path.
+torch::Tensor hgbt_hist(
+    torch::Tensor bins, torch::Tensor bin_off, torch::Tensor grp_off,
+    torch::Tensor node, torch::Tensor gq, torch::Tensor hq,
+    int64_t n_nodes, int64_t total_bins, int64_t lds_entries,
+    int64_t rows_per_block)
+{
+  TORCH_CHECK(bins.is_cuda() && bins.scalar_type() == torch::kUInt8 &&
+              bins.dim() == 2 && bins.is_contiguous(),
+              "bins must be a contiguous u8[F, N] GPU tensor");
+  const int64_t F = bins.size(0), N = bins.size(1);
+  hgbt_check(bin_off, bins, torch::kInt32, "bin_off");
+  hgbt_check(grp_off, bins, torch::kInt32, "grp_off");
+  hgbt_check(node, bins, torch::kInt32, "node");
+  hgbt_check(gq, bins, torch::kInt32, "gq");
+  hgbt_check(hq, bins, torch::kInt32, "hq");
+  TORCH_CHECK(F >= 1 && F <= 65535, "feature count out of range");
+  TORCH_CHECK(bin_off.dim() == 1 && bin_off.size(0) == F + 1, "bin_off must be i32[F+1]");
+  TORCH_CHECK(grp_off.dim() == 1 && grp_off.size(0) >= 2 && grp_off.size(0) <= F + 1,
+              "grp_off must be i32[groups+1]");
+  TORCH_CHECK(node.numel() == N && gq.numel() == N && hq.numel() == N,
+              "node, gq and hq must have one entry per row");
+  TORCH_CHECK(n_nodes >= 1 && total_bins >= 1 &&
+              total_bins <= F * HGBT_MAX_BINS &&
+              n_nodes * 3 * total_bins < (int64_t(1) << 31),
+              "histogram shape out of range");
+  TORCH_CHECK(rows_per_block >= 1 && rows_per_block <= HGBT_MAX_ROWS_PER_BLOCK,
+              "rows_per_block must keep int32 LDS partials in range (<= ",
+              HGBT_MAX_ROWS_PER_BLOCK, ")");
+  TORCH_CHECK(lds_entries >= 0 &&
+              (size_t)lds_entries * sizeof(int) <= HGBT_LDS_BYTES_MAX,
+              "LDS slab larger than the CU's LDS");
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)bins.get_device());
+  auto hist = torch::zeros({n_nodes, 3, total_bins},
+      torch::TensorOptions().dtype(torch::kInt64).device(bins.device()));
+  if (N == 0) return hist;
+  const int64_t row_blocks = (N + rows_per_block - 1) / rows_per_block;
+  TORCH_CHECK(row_blocks < (int64_t(1) << 31), "too many rows");
+
+  static bool lds_opt_in = false;
+  if (!lds_opt_in) {  // dynamic LDS above 64 KiB needs the opt-in once
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&hgbt_hist_kernel),
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)HGBT_LDS_BYTES_MAX));
+    lds_opt_in = true;
+  }
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(hgbt_hist_kernel,
+      dim3((unsigned)row_blocks, (unsigned)(grp_off.size(0) - 1)), dim3(HGBT_BLOCK),
+      (size_t)lds_entries * sizeof(int), stream,
+      bins.data_ptr<uint8_t>(), bin_off.data_ptr<int>(), grp_off.data_ptr<int>(),
+      node.data_ptr<int>(), gq.data_ptr<int>(), hq.data_ptr<int>(),
+      (long long)N, (int)F, (int)n_nodes, (int)total_bins, (int)rows_per_block,
+      (int)lds_entries,
+      reinterpret_cast<unsigned long long*>(hist.data_ptr<int64_t>()));
+  HIP_CHECK(hipGetLastError());
+  return hist;
+}
+
+// Best split per open node: i64[n_nodes, HGBT_REC] records.
+torch::Tensor hgbt_split(torch::Tensor hist, torch::Tensor bin_off,
+                         double lam, int64_t min_leaf)
+{
+  TORCH_CHECK(hist.is_cuda() && hist.scalar_type() == torch::kInt64 &&
+              hist.dim() == 3 && hist.size(1) == 3 && hist.is_contiguous(),
+              "hist must be a contiguous i64[n_nodes, 3, total_bins] GPU tensor");
+  hgbt_check(bin_off, hist, torch::kInt32, "bin_off");
+  TORCH_CHECK(bin_off.dim() == 1 && bin_off.size(0) >= 2, "bin_off must be i32[F+1]");
+  TORCH_CHECK(min_leaf >= 1, "min_leaf must be >= 1");
+  c10::hip::HIPGuard guard((c10::DeviceIndex)hist.get_device());
+  const int64_t K = hist.size(0);
+  auto out = torch::zeros({K, HGBT_REC},
+      torch::TensorOptions().dtype(torch::kInt64).device(hist.device()));
+  if (K == 0) return out;
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(hgbt_split_kernel, dim3((unsigned)K), dim3(HGBT_BLOCK), 0, stream,
+      reinterpret_cast<const long long*>(hist.data_ptr<int64_t>()),
+      bin_off.data_ptr<int>(), (int)(bin_off.size(0) - 1), (int)hist.size(2), lam, (long long)min_leaf,
+      reinterpret_cast<long long*>(out.data_ptr<int64_t>()));
+  HIP_CHECK(hipGetLastError());
+  return out;
+}
+
+// Move every open row to its child (in place on `node`).
+void hgbt_route(torch::Tensor bins, torch::Tensor table, torch::Tensor node)
+{
+  TORCH_CHECK(bins.is_cuda() && bins.scalar_type() == torch::kUInt8 &&
+              bins.dim() == 2 && bins.is_contiguous(),
+              "bins must be a contiguous u8[F, N] GPU tensor");
+  hgbt_check(table, bins, torch::kInt32, "table");
+  hgbt_check(node, bins, torch::kInt32, "node");
+  TORCH_CHECK(table.dim() == 2 && table.size(1) == 4, "table must be i32[n_nodes, 4]");
+  const int64_t N = bins.size(1);
+  TORCH_CHECK(node.numel() == N, "node must have one entry per row");
+  if (N == 0 || table.size(0) == 0) return;
+  const int64_t blocks = (N + HGBT_BLOCK - 1) / HGBT_BLOCK;
+  TORCH_CHECK(blocks < (int64_t(1) << 31), "too many rows");
+  c10::hip::HIPGuard guard((c10::DeviceIndex)bins.get_device());
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(hgbt_route_kernel, dim3((unsigned)blocks), dim3(HGBT_BLOCK), 0, stream,
+      bins.data_ptr<uint8_t>(), reinterpret_cast<const int4*>(table.data_ptr<int>()),
+      (long long)N, (int)bins.size(0), (int)table.size(0), node.data_ptr<int>());
+  HIP_CHECK(hipGetLastError());
+}
+
 torch::Tensor forest_ilp_bench(
     torch::Tensor codes, torch::Tensor nums,
     torch::Tensor nodes, torch::Tensor off,
@@ -2800,6 +3151,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("leaf_off"), py::arg("splits"), py::arg("medians"),
         py::arg("cls_kind"), py::arg("n_trees"),
         py::arg("block_target") = 2048);
+  m.def("hgbt_hist", &hgbt_hist,
+        "HistGBT level histogram i64[n_nodes,3,total_bins] of int32 "
+        "fixed-point gradients (gfx950)",
+        py::arg("bins"), py::arg("bin_off"), py::arg("grp_off"),
+        py::arg("node"), py::arg("gq"), py::arg("hq"), py::arg("n_nodes"),
+        py::arg("total_bins"), py::arg("lds_entries"),
+        py::arg("rows_per_block") = HGBT_MAX_ROWS_PER_BLOCK);
+  m.def("hgbt_split", &hgbt_split,
+        "HistGBT best split per open node, i64[n_nodes,9] records (gfx950)",
+        py::arg("hist"), py::arg("bin_off"), py::arg("lam"), py::arg("min_leaf"));
+  m.def("hgbt_route", &hgbt_route,
+        "HistGBT: move rows to their child node or leaf, in place (gfx950)",
+        py::arg("bins"), py::arg("table"), py::arg("node"));
+  m.attr("HGBT_SHIFT") = py::int_(HGBT_SHIFT);
+  m.attr("HGBT_MAX_ROWS_PER_BLOCK") = py::int_(HGBT_MAX_ROWS_PER_BLOCK);
+  m.attr("HGBT_LDS_BYTES_MAX") = py::int_(HGBT_LDS_BYTES_MAX);
   m.def("drift_stats", &drift_stats,
         "Per-feature drift statistics: categorical histograms + K-S D (gfx950)");
   m.def("encode_records", &encode_records,
