@@ -70,11 +70,21 @@ def ks_asymp_pvalue_many(ds: np.ndarray, n_ref: int, n_batch: int) -> np.ndarray
     latency. For en >= 300 the Pelz-Good series agrees with the exact value
     to < 3e-7 absolute (verified in tests at en = 974: < 1e-8), so the hot
     path uses a vectorized Pelz-Good; smaller en falls back to exact scipy.
+    The one corner where the series misses that bound at en >= 300 is tiny D
+    at en < ~320 (3.4e-7 at en = 300, D = 0.022), so for en < 500 the
+    values with en * D^1.5 <= 1.4 (where scipy itself prefers its exact
+    method) go to scipy as well — the same rule as the C epilogue
+    (csrc drift_pvals_raw).
     """
     en = int(np.round(float(n_ref) * float(n_batch) / (float(n_ref) + float(n_batch))))
     ds = np.asarray(ds, dtype=np.float64)
     if en >= 300:
-        return _pelz_good_sf(ds, en)
+        out = _pelz_good_sf(ds, en)
+        if en < 500:
+            small = np.atleast_1d(en * np.maximum(ds, 0.0) ** 1.5 <= 1.4)
+            if small.any():
+                out[small] = np.clip(stats.kstwo.sf(np.atleast_1d(ds)[small], en), 0.0, 1.0)
+        return out
     return np.clip(stats.kstwo.sf(ds, en), 0.0, 1.0)
 
 

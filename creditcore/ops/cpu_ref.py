@@ -318,7 +318,7 @@ def pvals_from_stats(
 
     # ref columns all have n_ref rows (fitted on one matrix)
     n_ref = int(packed.ref_sorted_offsets[1] - packed.ref_sorted_offsets[0])
-    if True:  # native epilogue: exact MTW for en<=140, Pelz-Good above
+    if True:  # native epilogue: scipy kstwo.sf's own region selection, in C
         from . import gpu
 
         if gpu.available():

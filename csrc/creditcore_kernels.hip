@@ -2642,8 +2642,12 @@ py::tuple encode_json_impl(const JsonEncoderState& st, py::bytes body) {
 // closed forms for integer dof (even: Poisson tail sum; odd: erfc +
 // half-integer-gamma series, both from the Q(k+2) = Q(k) + term recurrence)
 // and the Pelz-Good series for the two-sample K-S p-value (mirrors
-// creditcore.models.drift._pelz_good_sf; validated against scipy in tests).
-// Replaces ~0.4 ms of numpy/scipy per request with ~5 µs.
+// creditcore.models.drift._pelz_good_sf; validated against scipy in
+// tests/test_drift_pvals_host.py).
+// Replaces ~0.4 ms of numpy/scipy per request with ~5 µs on the Pelz-Good
+// path (en >= 300, the serving batch sizes). Small batches cost more: the
+// exact matrix (en <= 140, and tiny D below en = 500) and the Smirnov sum
+// (140 < en < 300, up to en terms per drifted column) are not timed here.
 // ---------------------------------------------------------------------------
 
 static double chi2_sf_int_dof(double x, int dof) {
@@ -2672,9 +2676,9 @@ static double chi2_sf_int_dof(double x, int dof) {
 }
 
 // Exact P(D_n > d) for small n via the Marsaglia-Tsang-Wang (2003) matrix
-// method (the same algorithm scipy's exact path uses for n <= 140). k-d
-// band is small in practice (k ~ ceil(n d) ~ sqrt(n) near the null); the
-// sf underflows to 0 for n d^2 > 18 long before m gets large.
+// method (Durbin's matrix, one of the exact algorithms scipy's kstwo picks
+// from). k-d band is small in practice (k ~ ceil(n d) ~ sqrt(n) near the
+// null); the sf underflows to 0 for n d^2 > 18 long before m gets large.
 static double mtw_sf(int n, double d) {
   if (d <= 0.0) return 1.0;
   if (d >= 1.0) return 0.0;
@@ -2797,6 +2801,24 @@ static double pelz_good_sf(double x, double n) {
   return std::min(1.0, std::max(0.0, 1.0 - cdf));
 }
 
+// One-sided Smirnov tail P(D_n^+ >= x), 0 < x < 1, by the Birnbaum-Tingey
+// sum x * sum_j C(n,j) (x + j/n)^(j-1) (1 - x - j/n)^(n-j), j <= n(1-x).
+// All terms are positive; each is formed in logs, with log C(n,j) carried
+// from term to term (three logs and one exp per term, at most n terms).
+static double smirnov_sf(int n, double x) {
+  const int jmax = (int)std::floor(n * (1.0 - x));
+  double sum = 0.0;
+  double log_c = 0.0;  // log C(n, j)
+  for (int j = 0; j <= jmax; ++j) {
+    if (j > 0) log_c += std::log((double)(n - j + 1) / j);
+    const double a = x + (double)j / n;
+    const double b = 1.0 - x - (double)j / n;
+    if (b <= 0.0) continue;  // j = n (1 - x) exactly: the term is 0
+    sum += std::exp(log_c + (j - 1) * std::log(a) + (n - j) * std::log(b));
+  }
+  return std::min(1.0, std::max(0.0, x * sum));
+}
+
 static void drift_pvals_raw(const int32_t* bh, const float* kd, int nnum,
                             const int32_t* rc, const int32_t* off, int ncat,
                             int64_t n_ref, int64_t n_batch, double* pv) {
@@ -2827,12 +2849,31 @@ static void drift_pvals_raw(const int32_t* bh, const float* kd, int nnum,
 
   const double en_f = (double)n_ref * (double)n_batch / ((double)n_ref + (double)n_batch);
   const double en = std::nearbyint(en_f);
-  // en <= 140: exact MTW (matches scipy's exact small-n path);
-  // en > 140: Pelz-Good series (<= 3e-7 abs vs exact, tested)
-  if (en <= 140.0) {
-    for (int j = 0; j < nnum; ++j) pv[ncat + j] = mtw_sf((int)en, (double)kd[j]);
-  } else {
-    for (int j = 0; j < nnum; ++j) pv[ncat + j] = pelz_good_sf((double)kd[j], en);
+  // The target is scipy.stats.kstwo.sf(D, en), what ks_2samp(method="asymp")
+  // and so models/drift.ks_asymp_pvalue report. Above n = 140 scipy itself
+  // (Simard & L'Ecuyer 2011) selects by region, and so does this:
+  //   en <= 140: exact MTW;
+  //   en D^2 >= 2.2: twice the one-sided Smirnov tail. Below en = 300 it is
+  //     evaluated as such (Pelz-Good is 5e-7 off it at en = 141); from 300
+  //     on Pelz-Good stands in, measured <= 1.1e-7 from it;
+  //   en D^1.5 <= 1.4: Durbin's exact matrix, i.e. MTW (k <= 1.25 en^(1/3)
+  //     + 1, a small matrix). Pelz-Good misses it by 3e-6 at en = 141 and
+  //     3.4e-7 at en = 300 but < 3e-7 from en = 320, so this stops at 500;
+  //   otherwise Pelz-Good, the same series as scipy's.
+  // Checked against kstwo.sf to 3e-7 in tests/test_drift_pvals_host.py.
+  for (int j = 0; j < nnum; ++j) {
+    const double d = (double)kd[j];
+    double p;
+    if (en <= 140.0) {
+      p = mtw_sf((int)en, d);
+    } else if (en < 300.0 && d > 0.0 && d < 1.0 && (en * d) * d >= 2.2) {
+      p = std::min(1.0, 2.0 * smirnov_sf((int)en, d));
+    } else if (en < 500.0 && en * d * std::sqrt(std::max(d, 0.0)) <= 1.4) {
+      p = mtw_sf((int)en, d);
+    } else {
+      p = pelz_good_sf(d, en);
+    }
+    pv[ncat + j] = p;
   }
 }
 
