@@ -1,7 +1,8 @@
-"""Training micro-benchmark: HistGBTClassifier on the GPU vs sklearn.
+"""Training micro-benchmark: the GPU trainers vs sklearn.
 
     python bench/train_micro.py --rows 20000
     python bench/train_micro.py --rows 1000000 --skip-exact-gbt
+    python bench/train_micro.py --mode forest --rows 20000 --depth 8
 
 Every estimator gets the same preprocessed matrix (the pipeline's
 [one-hot | 14 numerics] feature space, dense f32), the same 80/20 split and
@@ -10,6 +11,11 @@ estimator with the fit wall time (host binning and transfers included for
 hgbt) and the held-out log-loss, then one summary line. sklearn's exact
 GradientBoostingClassifier is single-threaded; --skip-exact-gbt leaves it out
 at row counts where it would run for many minutes.
+
+``--mode forest`` times HistForestClassifier (hrf; host binning, bootstrap
+draws and transfers included) against sklearn RandomForestClassifier on
+``--sklearn-jobs`` threads at equal n_estimators / max_depth / max_features,
+and reports the held-out log-loss and ROC-AUC of both.
 """
 
 from __future__ import annotations
@@ -43,8 +49,51 @@ def _log_loss(y, p) -> float:
     return float(-np.mean(y * np.log(p) + (1 - y) * np.log(1 - p)))
 
 
+def _forest(a, xtr, xte, ytr, yte, shape) -> None:
+    from sklearn.ensemble import RandomForestClassifier
+    from sklearn.metrics import roc_auc_score
+
+    from creditcore.models.hrf import HistForestClassifier
+
+    common = {"n_estimators": a.trees, "max_depth": a.depth,
+              "max_features": a.max_features, "random_state": a.seed}
+    ours = f"hrf[{a.device}]"
+    makers = {
+        ours: (lambda: HistForestClassifier(**common, device=a.device), a.repeats),
+        "sklearn_rf": (lambda: RandomForestClassifier(**common, n_jobs=a.sklearn_jobs), 1),
+    }
+    results = {}
+    for name, (make, repeats) in makers.items():
+        fits = []
+        for _ in range(repeats):
+            est = make()
+            t = time.perf_counter()
+            est.fit(xtr, ytr)
+            fits.append(time.perf_counter() - t)
+        p = est.predict_proba(xte)[:, 1]
+        results[name] = {"estimator": name, "fit_s": round(min(fits), 4),
+                         "fit_s_all": [round(f, 4) for f in fits],
+                         "log_loss": round(_log_loss(yte, p), 6),
+                         "roc_auc": round(float(roc_auc_score(yte, p)), 6)}
+        print(json.dumps(results[name]), flush=True)
+    print(json.dumps({
+        "event": "summary", **shape, "max_features": a.max_features,
+        "sklearn_jobs": a.sklearn_jobs,
+        **{f"{k}_{m}": v[m] for k, v in results.items()
+           for m in ("fit_s", "log_loss", "roc_auc")},
+        "speedup_vs_sklearn_rf": round(
+            results["sklearn_rf"]["fit_s"] / results[ours]["fit_s"], 2),
+    }), flush=True)
+
+
 def main(argv=None) -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", default="gbt", choices=["gbt", "forest"],
+                    help="gbt = hgbt vs sklearn boosting; forest = hrf vs sklearn RF")
+    ap.add_argument("--max-features", default="sqrt",
+                    help="forest mode: 'sqrt', an integer or 'none'")
+    ap.add_argument("--sklearn-jobs", type=int, default=16,
+                    help="forest mode: threads of sklearn's RandomForestClassifier")
     ap.add_argument("--rows", type=int, default=20_000)
     ap.add_argument("--trees", type=int, default=100)
     ap.add_argument("--depth", type=int, default=6)
@@ -67,6 +116,12 @@ def main(argv=None) -> None:
              "trees": a.trees, "depth": a.depth, "learning_rate": a.learning_rate}
     print(json.dumps({"event": "data", **shape,
                       "prep_s": round(time.perf_counter() - t0, 3)}), flush=True)
+
+    if a.mode == "forest":
+        mf = a.max_features.lower()
+        a.max_features = None if mf == "none" else mf if mf == "sqrt" else int(mf)
+        shape.pop("learning_rate")
+        return _forest(a, xtr, xte, ytr, yte, shape)
 
     common = {"n_estimators": a.trees, "max_depth": a.depth,
               "learning_rate": a.learning_rate}

@@ -28,14 +28,16 @@ def _cmd_train(argv):
     p.add_argument("--min-roc-auc", type=float, default=None,
                    help="refuse to register below this validation ROC-AUC "
                         "(the quality gate the reference lacks)")
-    p.add_argument("--algorithm", default="rf", choices=["rf", "gbt", "et", "hgbt"],
+    p.add_argument("--algorithm", default="rf", choices=["rf", "gbt", "et", "hgbt", "hrf"],
                    help="rf = the reference's RandomForest; et = ExtraTrees "
                         "(same packed format/kernel); gbt = "
                         "gradient-boosted trees (same HIP traversal kernel); "
-                        "hgbt = histogram gradient boosting trained on the GPU")
+                        "hgbt = histogram gradient boosting trained on the GPU; "
+                        "hrf = histogram random forest trained on the GPU")
     p.add_argument("--train-device", default="auto", choices=["auto", "cpu", "cuda"],
-                   help="where --algorithm hgbt trains: auto = the GPU when "
-                        "one is visible (the other families train with sklearn)")
+                   help="where --algorithm hgbt / hrf train: auto = the GPU "
+                        "when one is visible (the other families train with "
+                        "sklearn on the host)")
     p.add_argument("--data", default=None,
                    help="CSV with the UCI schema (the reference's curated "
                         "table, 00-create-external-table.ipynb); synthetic "

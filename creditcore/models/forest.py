@@ -9,7 +9,8 @@ Reproduces the reference's sklearn pipeline exactly
                n_jobs=-1)
 
 Training happens on CPU with sklearn (like the reference), except for the
-"hgbt" family, which trains on the GPU (models/hgbt.py); *scoring* happens
+"hgbt" and "hrf" families, which train on the GPU (models/hgbt.py,
+models/hrf.py); *scoring* happens
 on MI355X via the packed flat-buffer representation (creditcore.pack) and the
 HIP forest-traversal kernel (csrc/creditcore_kernels.hip (forest_kernel_ilpN)). This module is the
 golden CPU path the GPU path is tested against.
@@ -36,7 +37,10 @@ def make_classifier_pipeline(params: dict, algorithm: str = "rf") -> Pipeline:
     kernel with a sigmoid(sum + prior) finalize), "hgbt"
     (models.hgbt.HistGBTClassifier — histogram gradient boosting trained by
     HIP kernels on the GPU, packed and scored like "gbt"; ``params`` may
-    carry ``device`` for the training device), or "et"
+    carry ``device`` for the training device), "hrf"
+    (models.hrf.HistForestClassifier — the random forest trained by HIP
+    kernels, many trees per launch, packed and scored like "rf"; takes
+    ``device`` too), or "et"
     (ExtraTreesClassifier — identical tree structure and leaf-fraction-mean
     semantics to RF, so it rides the RF pack/score path unchanged).
     """
@@ -56,6 +60,14 @@ def make_classifier_pipeline(params: dict, algorithm: str = "rf") -> Pipeline:
         if "max_depth" in params:  # the search space draws up to 24
             params["max_depth"] = min(int(params["max_depth"]), MAX_DEPTH)
         estimator = HistGBTClassifier(**params)
+    elif algorithm == "hrf":
+        from .hrf import MAX_DEPTH, HistForestClassifier
+
+        params = dict(params)
+        params.pop("criterion", None)  # Gini only (models/hrf.py)
+        if "max_depth" in params:  # the search space draws up to 24
+            params["max_depth"] = min(int(params["max_depth"]), MAX_DEPTH)
+        estimator = HistForestClassifier(**params)
     elif algorithm == "et":
         from sklearn.ensemble import ExtraTreesClassifier
 

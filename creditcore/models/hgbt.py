@@ -130,15 +130,16 @@ class _CpuBackend:
 
 
 def plan_feature_groups(
-    n_bins: np.ndarray, n_nodes: int, lds_bytes: int, max_feats: int
+    n_bins: np.ndarray, n_nodes: int, lds_bytes: int, max_feats: int, planes: int = 3
 ) -> tuple[np.ndarray, int]:
     """Feature groups of one histogram launch (grid.y) and the int32 entry
-    count of the largest group's LDS slab, n_nodes * 3 * group bins.
+    count of the largest group's LDS slab, n_nodes * planes * group bins
+    (3 planes here; models/hrf.py plans its 2-plane histogram with this too).
 
     Consecutive features are packed while the slab stays within ``lds_bytes``
     and the group within ``max_feats`` features. A level whose single widest
     feature does not fit gets slab 0: the direct-global path."""
-    per_bin = 3 * int(n_nodes)
+    per_bin = int(planes) * int(n_nodes)
     cap = lds_bytes // 4
     fits = per_bin * int(n_bins.max()) <= cap
     off, cur_bins, cur_feats, widest = [0], 0, 0, 0

@@ -469,3 +469,159 @@ def hgbt_route_cpu(bins: np.ndarray, table: np.ndarray, node: np.ndarray) -> np.
     go_left = (feat < 0) | (b <= t[:, 1])
     out[live] = np.where(go_left, t[:, 2], t[:, 3]).astype(node.dtype)
     return out
+
+
+# ---------------------------------------------------------------------------
+# Histogram random-forest trainer: the three level primitives over a batch of
+# trees (golden reference of hrf_hist / hrf_split / hrf_route in
+# csrc/creditcore_kernels.hip). A level is a flat list of open slots;
+# ``slot_off i32[TB+1]`` gives each tree's range in it and
+# ``slot_meta i32[K, 2]`` = (global tree index, node id) per slot. Everything
+# is an integer or the same f64 formula: the kernels match with exact equality.
+# ---------------------------------------------------------------------------
+
+HRF_REC = 7  # split record: proxy bits, feat, bin, PL, WL, P, W
+# odd 64-bit multipliers of the per-node feature key (also in the .hip file)
+HRF_C1 = 0x9E3779B97F4A7C15  # tree
+HRF_C2 = 0xC2B2AE3D27D4EB4F  # node id
+HRF_C3 = 0x165667B19E3779F9  # feature
+_U64 = (1 << 64) - 1
+
+
+def hrf_feature_keys(seed: int, tree, node_id, n_feat: int) -> np.ndarray:
+    """u64[..., n_feat] feature keys of one or many nodes:
+    splitmix64_finalizer(seed ^ tree*C1 ^ node_id*C2 ^ f*C3), all mod 2^64.
+    A node's features are ranked by (key, f) ascending; the first
+    ``max_features`` ranks are its candidates (hrf_split_cpu)."""
+    u = np.uint64
+    tree = np.asarray(tree, dtype=np.int64).astype(u)[..., None]
+    node_id = np.asarray(node_id, dtype=np.int64).astype(u)[..., None]
+    f = np.arange(n_feat, dtype=u)
+    with np.errstate(over="ignore"):
+        z = u(int(seed) & _U64) ^ (tree * u(HRF_C1)) ^ (node_id * u(HRF_C2)) ^ (f * u(HRF_C3))
+        z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+        return z ^ (z >> u(31))
+
+
+def hrf_hist_cpu(
+    bins: np.ndarray,
+    bin_off: np.ndarray,
+    y: np.ndarray,
+    w: np.ndarray,
+    node: np.ndarray,
+    slot_off: np.ndarray,
+) -> np.ndarray:
+    """Level histogram i64[K, 2, total_bins] with planes {sum w*y, sum w}.
+
+    ``bins`` u8[F, N] and ``y`` u8[N] (0/1) are shared by the batch;
+    ``w`` u8[TB, N] are the trees' bootstrap counts and ``node`` i32[TB, N]
+    the row's local slot within its tree (negative: in a leaf, or weight 0).
+    Tree t's local slot s is row ``slot_off[t] + s`` of the result."""
+    n_feat = bins.shape[0]
+    total = int(bin_off[-1])
+    hist = np.zeros((int(slot_off[-1]), 2, total), dtype=np.int64)
+    for t in range(len(slot_off) - 1):
+        s0, k = int(slot_off[t]), int(slot_off[t + 1] - slot_off[t])
+        live = np.flatnonzero((node[t] >= 0) & (node[t] < k))
+        if k == 0 or not len(live):
+            continue
+        nd = node[t, live].astype(np.int64)
+        wt = w[t, live].astype(np.int64)
+        wy = wt * y[live]
+        for f in range(n_feat):
+            a, b = int(bin_off[f]), int(bin_off[f + 1])
+            nb = b - a
+            idx = nd * nb + bins[f, live]
+            # bincount sums in f64: exact, every sum is an integer < 2^53
+            for plane, val in ((0, wy), (1, wt)):
+                hist[s0 : s0 + k, plane, a:b] = np.bincount(
+                    idx, weights=val, minlength=k * nb
+                ).astype(np.int64).reshape(k, nb)
+    return hist
+
+
+def hrf_split_cpu(
+    hist: np.ndarray,
+    bin_off: np.ndarray,
+    slot_meta: np.ndarray,
+    max_features: int,
+    min_leaf: int,
+    seed: int,
+) -> np.ndarray:
+    """Chosen split per open slot, i64[K, HRF_REC].
+
+    "bin <= b goes left" of feature f has the Gini proxy
+    PL^2/WL + PR^2/WR - P^2/W (P positives, W weight) in f64 from the integer
+    sums; it is valid when WL >= min_leaf, WR >= min_leaf and proxy > 0. A
+    feature's best split is its highest valid proxy, ties to the lowest bin.
+    Features are ranked by (hrf_feature_keys, f); the candidates are the
+    first max(max_features, r* + 1) ranks, r* the lowest rank that has a valid
+    split, and the slot takes the candidate with the highest proxy, ties to
+    the lower rank. No valid split anywhere: feat = -1 and zeros. P and W are
+    always reported. The kernel evaluates the same expression in the same
+    order with contraction off."""
+    n_slots, _, total = hist.shape
+    bin_off = np.asarray(bin_off, dtype=np.int64)
+    n_feat = len(bin_off) - 1
+    out = np.zeros((n_slots, HRF_REC), dtype=np.int64)
+    if n_slots == 0:
+        return out
+    feat_of_bin = np.repeat(np.arange(n_feat), np.diff(bin_off))
+    start = bin_off[:-1][feat_of_bin]
+    cs = np.cumsum(hist, axis=2)
+    before = np.where(start > 0, cs[:, :, np.maximum(start - 1, 0)], 0)
+    pre = cs - before  # prefix sums within each feature
+    PL, WL = pre[:, 0], pre[:, 1]
+    tot = pre[:, :, int(bin_off[1]) - 1]  # feature 0 sees every open row
+    P, W = tot[:, 0:1], tot[:, 1:2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        pl, wl = PL.astype(np.float64), WL.astype(np.float64)
+        pr, wr = (P - PL).astype(np.float64), (W - WL).astype(np.float64)
+        p, w = P.astype(np.float64), W.astype(np.float64)
+        a = (pl * pl) / wl
+        b = (pr * pr) / wr
+        c = (p * p) / w
+        proxy = (a + b) - c
+        valid = (WL >= min_leaf) & (W - WL >= min_leaf) & (proxy > 0.0)
+    proxy = np.where(valid, proxy, -np.inf)
+    # per feature: highest proxy, then the first bin that reaches it
+    f_best = np.maximum.reduceat(proxy, bin_off[:-1], axis=1)  # [K, F]
+    at_best = valid & (proxy == f_best[:, feat_of_bin])
+    pos = np.where(at_best, np.arange(total), total)
+    f_pos = np.minimum.reduceat(pos, bin_off[:-1], axis=1)  # flat bin index
+    f_valid = f_pos < total
+
+    keys = hrf_feature_keys(seed, slot_meta[:, 0], slot_meta[:, 1], n_feat)
+    order = np.argsort(keys, axis=1, kind="stable")  # rank -> feature, ties by f
+    v_ranked = np.take_along_axis(f_valid, order, axis=1)
+    any_valid = v_ranked.any(axis=1)
+    r_star = np.argmax(v_ranked, axis=1)  # first valid rank
+    limit = np.maximum(int(max_features), r_star + 1)
+    cand = v_ranked & (np.arange(n_feat) < limit[:, None])
+    p_ranked = np.where(cand, np.take_along_axis(f_best, order, axis=1), -np.inf)
+    k = np.arange(n_slots)
+    feat = order[k, np.argmax(p_ranked, axis=1)]  # first maximum: lower rank
+    at = np.where(any_valid, f_pos[k, feat], 0)
+    out[:, 0] = np.where(any_valid, f_best[k, feat], 0.0).view(np.int64)
+    out[:, 1] = np.where(any_valid, feat, -1)
+    out[:, 2] = np.where(any_valid, at - start[at], 0)
+    out[:, 3] = np.where(any_valid, PL[k, at], 0)
+    out[:, 4] = np.where(any_valid, WL[k, at], 0)
+    out[:, 5:7] = tot
+    return out
+
+
+def hrf_route_cpu(
+    bins: np.ndarray, table: np.ndarray, node: np.ndarray, slot_off: np.ndarray
+) -> np.ndarray:
+    """New node ids i32[TB, N]. ``table[slot_off[t] + s] = {feat, bin, left,
+    right}`` for local slot s of tree t, with hgbt_route_cpu's protocol:
+    bins[feat] <= bin takes ``left``, the rest ``right``; feat < 0 closes the
+    slot and every row takes ``left``. Targets >= 0 are local slots of the
+    tree's next level, negative ones encode leaf node i as -(i + 1)."""
+    out = node.copy()
+    for t in range(len(slot_off) - 1):
+        a, b = int(slot_off[t]), int(slot_off[t + 1])
+        out[t] = hgbt_route_cpu(bins, table[a:b], node[t])
+    return out

@@ -311,8 +311,9 @@ def pack_classifier_pipeline(pipeline) -> dict:
     sklearn pipeline built by make_classifier_pipeline. Supports the
     reference's RandomForestClassifier (leaf-fraction mean),
     GradientBoostingClassifier (lr-scaled regression leaves summed into a
-    logit on top of the prior) and models.hgbt.HistGBTClassifier (the same
-    finalize, from the estimator's own flat arrays)."""
+    logit on top of the prior), models.hgbt.HistGBTClassifier (the same
+    finalize, from the estimator's own flat arrays) and
+    models.hrf.HistForestClassifier (leaf-fraction mean, from flat arrays)."""
     pre = pipeline.named_steps["preprocessor"]
     clf = pipeline.named_steps["classifier"]
 
@@ -340,6 +341,18 @@ def pack_classifier_pipeline(pipeline) -> dict:
         # inputs, leaves already scaled by the learning rate, integer covers
         cls_kind = 1
         cls_bias = float(clf.init_raw_)
+        for i in range(clf.n_trees_):
+            t = clf.tree_arrays(i)
+            nd, nv, nc = _pack_tree_arrays(
+                t["children_left"], t["children_right"], t["feature"],
+                t["threshold"], t["value"], cover=t["cover"],
+            )
+            trees.append(nd)
+            values.append(nv)
+            covers.append(nc)
+    elif type(clf).__name__ == "HistForestClassifier":
+        # models/hrf.py: the same plain arrays; leaves are class-1 fractions
+        # P/W already rounded to f32, covers the integer bootstrap weights
         for i in range(clf.n_trees_):
             t = clf.tree_arrays(i)
             nd, nv, nc = _pack_tree_arrays(

@@ -62,10 +62,11 @@ class EvalRun:
 
 def _family_params(params: dict, algorithm: str, train_device: str) -> dict:
     """Map a draw from the reference search space onto the estimator family:
-    hgbt has no split criterion, caps max_depth and takes a training device."""
-    if algorithm != "hgbt":
+    hgbt and hrf have no split criterion choice (hrf is Gini only), cap
+    max_depth and take a training device."""
+    if algorithm not in ("hgbt", "hrf"):
         return params
-    from .models.hgbt import MAX_DEPTH
+    from .models.hgbt import MAX_DEPTH  # models/hrf.py shares the limit
 
     out = {k: v for k, v in params.items() if k != "criterion"}
     if "max_depth" in out:

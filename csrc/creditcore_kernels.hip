@@ -1539,6 +1539,428 @@ void hgbt_route(torch::Tensor bins, torch::Tensor table, torch::Tensor node)
   HIP_CHECK(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------
+// Histogram random-forest trainer (creditcore/models/hrf.py).
+//
+// A forest's trees are independent, so a batch of TB trees grows in the same
+// launches: one level of the whole batch = hrf_hist_kernel, hrf_split_kernel,
+// hrf_route_kernel and one copy of the split records to the host. The level
+// is a flat list of open slots; slot_off i32[TB+1] gives each tree's range in
+// it and slot_meta i32[K, 2] = (global tree index, node id) per slot.
+//
+// Layouts: bins u8[F, N] and y u8[N] (0/1) are shared by the batch; w u8[TB, N]
+// are the bootstrap counts and node i32[TB, N] the row's local slot within
+// its tree (negative: in a leaf, or weight 0). Histogram i64[K, 2, total_bins]
+// with planes {sum w*y, sum w}: integers, so order independent, and the CPU
+// reference (ops/cpu_ref.py hrf_*_cpu) must match bit for bit.
+// ---------------------------------------------------------------------------
+
+#define HRF_REC 7  // split record, i64 words: proxy bits, feat, bin, PL, WL, P, W
+#define HRF_MAX_FEATS 1024  // per-feature LDS tables of hrf_split_kernel
+// odd multipliers of the feature key (cpu_ref.HRF_C1..3)
+#define HRF_C1 0x9E3779B97F4A7C15ull
+#define HRF_C2 0xC2B2AE3D27D4EB4Full
+#define HRF_C3 0x165667B19E3779F9ull
+// A block's int32 LDS partial is at most rows_per_block * 255. The cap is far
+// below that bound on purpose: 32 rows per thread keep the slab flush a small
+// share of a block's work while (row blocks x groups x trees) still fills the
+// chip at a few thousand rows.
+static constexpr int64_t HRF_MAX_ROWS_PER_BLOCK = 32 * HGBT_BLOCK;
+static_assert(HRF_MAX_ROWS_PER_BLOCK * 255 < (int64_t(1) << 31),
+              "int32 LDS partials of hrf_hist_kernel would overflow");
+
+// grid = (row blocks, feature groups, tree in batch). lds_entries > 0: the
+// block's (open slots of its tree x 2 x group bins) slab is summed in LDS and
+// flushed with one global atomic per non-zero entry; lds_entries == 0: int64
+// atomics straight to global memory. Offsets read from slot_off / bin_off /
+// grp_off are range-checked before use: bad contents skip work.
+__global__ __launch_bounds__(HGBT_BLOCK) void hrf_hist_kernel(
+    const uint8_t* __restrict__ bins, const int* __restrict__ bin_off,
+    const int* __restrict__ grp_off, const uint8_t* __restrict__ y,
+    const uint8_t* __restrict__ w, const int* __restrict__ node,
+    const int* __restrict__ slot_off,
+    long long n_rows, int n_feat, int n_slots, int total_bins,
+    int rows_per_block, int lds_entries,
+    unsigned long long* __restrict__ hist)
+{
+  extern __shared__ int hrf_lds[];
+  const int tid = threadIdx.x;
+  const int t = blockIdx.z;
+  const int s0 = slot_off[t];
+  const int k = slot_off[t + 1] - s0;  // open slots of this tree
+  if (s0 < 0 || k <= 0 || (long long)s0 + k > n_slots) return;
+  const int f0 = grp_off[blockIdx.y], f1 = grp_off[blockIdx.y + 1];
+  if (f0 < 0 || f1 > n_feat || f0 >= f1) return;
+  const int b0 = bin_off[f0];
+  const int gb = bin_off[f1] - b0;  // bins of this feature group
+  if (b0 < 0 || gb <= 0 || (long long)b0 + gb > total_bins) return;
+  const bool use_lds = lds_entries > 0;
+  const long long slab = (long long)k * 2 * gb;
+  if (use_lds) {
+    if (slab > lds_entries) return;  // host sizes the allocation from the same tables
+    for (int i = tid; i < (int)slab; i += HGBT_BLOCK) hrf_lds[i] = 0;
+    __syncthreads();
+  }
+  unsigned long long* thist = hist + (size_t)s0 * 2 * total_bins;
+  const uint8_t* tw = w + (size_t)t * (size_t)n_rows;
+  const int* tnode = node + (size_t)t * (size_t)n_rows;
+
+  const long long r0 = (long long)blockIdx.x * rows_per_block;
+  const long long r1 = min(r0 + (long long)rows_per_block, n_rows);
+  for (long long r = r0 + tid; r < r1; r += HGBT_BLOCK) {
+    const int nd = tnode[r];
+    if (nd < 0 || nd >= k) continue;  // in a leaf, or out of the bootstrap
+    const int wt = tw[r];
+    if (wt == 0) continue;
+    const int wy = y[r] ? wt : 0;
+    for (int f = f0; f < f1; ++f) {
+      const int fb = bin_off[f];
+      const int nb = bin_off[f + 1] - fb;
+      if (fb < b0 || nb <= 0 || fb + nb > b0 + gb) continue;
+      const int b = bins[(size_t)f * (size_t)n_rows + (size_t)r];
+      if (b >= nb) continue;
+      if (use_lds) {
+        int* p = hrf_lds + (size_t)nd * 2 * gb + (fb - b0) + b;
+        if (wy) atomicAdd(p, wy);
+        atomicAdd(p + gb, wt);
+      } else {
+        unsigned long long* p = thist + (size_t)nd * 2 * total_bins + fb + b;
+        if (wy) atomicAdd(p, (unsigned long long)wy);
+        atomicAdd(p + total_bins, (unsigned long long)wt);
+      }
+    }
+  }
+
+  if (use_lds) {
+    __syncthreads();
+    for (int i = tid; i < (int)slab; i += HGBT_BLOCK) {
+      const int v = hrf_lds[i];
+      if (v == 0) continue;
+      const int plane = i / gb;  // local slot * 2 + {w*y, w}
+      const int b = i - plane * gb;
+      atomicAdd(thist + (size_t)plane * total_bins + b0 + b, (unsigned long long)v);
+    }
+  }
+}
+
+// Gini proxy PL^2/WL + PR^2/WR - P^2/W from the integer sums, in f64. The
+// operation order is hrf_split_cpu's and contraction is off (see hgbt_gain).
+__device__ __forceinline__ double hrf_proxy(
+    long long PL, long long WL, long long P, long long W)
+{
+#pragma clang fp contract(off)
+  const double pl = (double)PL, wl = (double)WL;
+  const double pr = (double)(P - PL), wr = (double)(W - WL);
+  const double p = (double)P, w = (double)W;
+  const double a = (pl * pl) / wl;
+  const double b = (pr * pr) / wr;
+  const double c = (p * p) / w;
+  return (a + b) - c;
+}
+
+__device__ __forceinline__ unsigned long long hrf_key(
+    unsigned long long seed, int tree, int node_id, int f)
+{
+  // int -> i64 -> u64, as cpu_ref.hrf_feature_keys converts
+  unsigned long long z = seed ^ ((unsigned long long)(long long)tree * HRF_C1)
+                              ^ ((unsigned long long)(long long)node_id * HRF_C2)
+                              ^ ((unsigned long long)f * HRF_C3);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+struct HrfPick {
+  double proxy;
+  int rank, feat;  // rank < 0 = nothing picked yet
+};
+
+// highest proxy, then the lower rank
+__device__ __forceinline__ bool hrf_better(const HrfPick& a, const HrfPick& b) {
+  if (a.rank < 0) return false;
+  if (b.rank < 0) return true;
+  if (a.proxy != b.proxy) return a.proxy > b.proxy;
+  return a.rank < b.rank;
+}
+
+// One block per open slot. Phase 1 (hgbt_split_kernel's scan): each wavefront
+// takes every 4th feature, a lane owns 4 bins, and the feature's best valid
+// split (highest proxy, lowest bin) goes to the LDS table. Phase 2: feature
+// keys, ranks by (key, f), r* = lowest rank with a valid split, and among the
+// ranks below max(max_features, r* + 1) the highest proxy, ties to the lower
+// rank.
+__global__ __launch_bounds__(HGBT_BLOCK) void hrf_split_kernel(
+    const long long* __restrict__ hist, const int* __restrict__ bin_off,
+    const int* __restrict__ slot_meta, int n_feat, int total_bins,
+    int max_features, long long min_leaf, unsigned long long seed,
+    long long* __restrict__ out)
+{
+  __shared__ double f_proxy[HRF_MAX_FEATS];
+  __shared__ unsigned long long f_key[HRF_MAX_FEATS];
+  __shared__ long long f_pl[HRF_MAX_FEATS], f_wl[HRF_MAX_FEATS];
+  __shared__ int f_bin[HRF_MAX_FEATS];  // -1: the feature has no valid split
+  __shared__ int f_rank[HRF_MAX_FEATS];
+  __shared__ long long tot[2];
+  __shared__ int r_star;
+  __shared__ HrfPick wave_pick[HGBT_BLOCK / 64];
+  const int k = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const long long* hp = hist + (size_t)k * 2 * total_bins;
+  const long long* hw = hp + total_bins;
+  if (n_feat > HRF_MAX_FEATS) return;  // the wrapper refuses this too
+
+  if (tid == 0) { r_star = n_feat; tot[0] = tot[1] = 0; }
+  for (int f = wave; f < n_feat; f += HGBT_BLOCK / 64) {
+    const int fb = bin_off[f];
+    const int nb = bin_off[f + 1] - fb;
+    double bp = 0.0;
+    int bb = -1;
+    long long bpl = 0, bwl = 0;
+    if (!(fb < 0 || nb <= 0 || nb > HGBT_MAX_BINS || fb + nb > total_bins)) {
+      long long pp[4], pw[4];
+      long long sp = 0, sw = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int b = lane * 4 + j;
+        if (b < nb) { sp += hp[fb + b]; sw += hw[fb + b]; }
+        pp[j] = sp; pw[j] = sw;
+      }
+      long long ip = sp, iw = sw;  // inclusive scan of the lane totals
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const long long tp = __shfl_up(ip, d), tw = __shfl_up(iw, d);
+        if (lane >= d) { ip += tp; iw += tw; }
+      }
+      const long long P = __shfl(ip, 63), W = __shfl(iw, 63);
+      // every feature sees every open row once: feature 0's totals are the slot's
+      if (f == 0 && lane == 0) { tot[0] = P; tot[1] = W; }
+      const long long op = ip - sp, ow = iw - sw;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int b = lane * 4 + j;
+        if (b >= nb) continue;
+        const long long WL = ow + pw[j], PL = op + pp[j];
+        if (WL < min_leaf || W - WL < min_leaf) continue;
+        const double px = hrf_proxy(PL, WL, P, W);
+        if (!(px > 0.0)) continue;
+        if (bb < 0 || px > bp) { bp = px; bb = b; bpl = PL; bwl = WL; }  // ascending b
+      }
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) {
+        const double op_ = __shfl_xor(bp, m);
+        const int ob = __shfl_xor(bb, m);
+        const long long opl = __shfl_xor(bpl, m), owl = __shfl_xor(bwl, m);
+        const bool take = ob >= 0 && (bb < 0 || op_ > bp || (op_ == bp && ob < bb));
+        if (take) { bp = op_; bb = ob; bpl = opl; bwl = owl; }
+      }
+    }
+    if (lane == 0) { f_proxy[f] = bp; f_bin[f] = bb; f_pl[f] = bpl; f_wl[f] = bwl; }
+  }
+  const int tree = slot_meta[2 * k], node_id = slot_meta[2 * k + 1];
+  for (int f = tid; f < n_feat; f += HGBT_BLOCK) f_key[f] = hrf_key(seed, tree, node_id, f);
+  __syncthreads();
+
+  for (int f = tid; f < n_feat; f += HGBT_BLOCK) {
+    const unsigned long long kf = f_key[f];
+    int rank = 0;
+    for (int g = 0; g < n_feat; ++g) {  // same g across the wave: LDS broadcast
+      const unsigned long long kg = f_key[g];
+      rank += (kg < kf || (kg == kf && g < f)) ? 1 : 0;
+    }
+    f_rank[f] = rank;
+    if (f_bin[f] >= 0) atomicMin(&r_star, rank);
+  }
+  __syncthreads();
+
+  const int limit = max(max_features, r_star + 1);
+  HrfPick best;
+  best.proxy = 0.0; best.rank = -1; best.feat = -1;
+  for (int f = tid; f < n_feat; f += HGBT_BLOCK) {
+    if (f_bin[f] < 0 || f_rank[f] >= limit) continue;
+    HrfPick c;
+    c.proxy = f_proxy[f]; c.rank = f_rank[f]; c.feat = f;
+    if (hrf_better(c, best)) best = c;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    HrfPick o;
+    o.proxy = __shfl_xor(best.proxy, m);
+    o.rank = __shfl_xor(best.rank, m);
+    o.feat = __shfl_xor(best.feat, m);
+    if (hrf_better(o, best)) best = o;
+  }
+  if (lane == 0) wave_pick[wave] = best;
+  __syncthreads();
+  if (tid == 0) {
+    for (int wv = 1; wv < HGBT_BLOCK / 64; ++wv)
+      if (hrf_better(wave_pick[wv], best)) best = wave_pick[wv];
+    long long* o = out + (size_t)k * HRF_REC;
+    const bool ok = best.rank >= 0;
+    o[0] = __double_as_longlong(ok ? best.proxy : 0.0);
+    o[1] = ok ? best.feat : -1;
+    o[2] = ok ? f_bin[best.feat] : 0;
+    o[3] = ok ? f_pl[best.feat] : 0;
+    o[4] = ok ? f_wl[best.feat] : 0;
+    o[5] = tot[0]; o[6] = tot[1];
+  }
+}
+
+// grid = (row blocks, tree). hgbt_route_kernel's table protocol with the
+// table indexed by slot_off[t] + local slot; targets are local slots of the
+// tree's next level or -(leaf node + 1).
+__global__ __launch_bounds__(HGBT_BLOCK) void hrf_route_kernel(
+    const uint8_t* __restrict__ bins, const int4* __restrict__ table,
+    const int* __restrict__ slot_off, long long n_rows, int n_feat, int n_slots,
+    int* __restrict__ node)
+{
+  const long long r = (long long)blockIdx.x * HGBT_BLOCK + threadIdx.x;
+  if (r >= n_rows) return;
+  const int t = blockIdx.y;
+  const int s0 = slot_off[t];
+  const int k = slot_off[t + 1] - s0;
+  if (s0 < 0 || k <= 0 || (long long)s0 + k > n_slots) return;
+  int* tnode = node + (size_t)t * (size_t)n_rows;
+  const int nd = tnode[r];
+  if (nd < 0 || nd >= k) return;
+  const int4 e = table[s0 + nd];
+  if (e.x < 0) {
+    tnode[r] = e.z;
+  } else if (e.x < n_feat) {
+    const int b = bins[(size_t)e.x * (size_t)n_rows + (size_t)r];
+    tnode[r] = (b <= e.y) ? e.z : e.w;
+  }
+}
+
+// Shared argument checks of the three hrf wrappers: returns TB.
+int64_t hrf_check_batch(const torch::Tensor& bins, const torch::Tensor& node,
+                        const torch::Tensor& slot_off, int64_t n_slots) {
+  TORCH_CHECK(bins.is_cuda() && bins.scalar_type() == torch::kUInt8 &&
+              bins.dim() == 2 && bins.is_contiguous(),
+              "bins must be a contiguous u8[F, N] GPU tensor");
+  hgbt_check(node, bins, torch::kInt32, "node");
+  hgbt_check(slot_off, bins, torch::kInt32, "slot_off");
+  TORCH_CHECK(node.dim() == 2 && node.size(1) == bins.size(1), "node must be i32[TB, N]");
+  const int64_t TB = node.size(0);
+  TORCH_CHECK(TB >= 1 && TB <= 65535, "tree batch out of range (1..65535)");
+  TORCH_CHECK(slot_off.dim() == 1 && slot_off.size(0) == TB + 1,
+              "slot_off must be i32[TB+1]");
+  TORCH_CHECK(n_slots >= 0, "n_slots must be >= 0");
+  return TB;
+}
+
+// Level histogram i64[n_slots, 2, total_bins] of a tree batch. lds_entries is
+// the int32 entry count of the largest (tree, feature group) slab, or 0 to
+// take the direct-global path. n_slots must equal slot_off[TB].
+torch::Tensor hrf_hist(
+    torch::Tensor bins, torch::Tensor bin_off, torch::Tensor grp_off,
+    torch::Tensor y, torch::Tensor w, torch::Tensor node, torch::Tensor slot_off,
+    int64_t n_slots, int64_t total_bins, int64_t lds_entries,
+    int64_t rows_per_block)
+{
+  const int64_t TB = hrf_check_batch(bins, node, slot_off, n_slots);
+  const int64_t F = bins.size(0), N = bins.size(1);
+  hgbt_check(bin_off, bins, torch::kInt32, "bin_off");
+  hgbt_check(grp_off, bins, torch::kInt32, "grp_off");
+  hgbt_check(y, bins, torch::kUInt8, "y");
+  hgbt_check(w, bins, torch::kUInt8, "w");
+  TORCH_CHECK(F >= 1 && F <= HRF_MAX_FEATS, "feature count out of range (1..",
+              HRF_MAX_FEATS, ")");
+  TORCH_CHECK(bin_off.dim() == 1 && bin_off.size(0) == F + 1, "bin_off must be i32[F+1]");
+  TORCH_CHECK(grp_off.dim() == 1 && grp_off.size(0) >= 2 && grp_off.size(0) <= F + 1,
+              "grp_off must be i32[groups+1]");
+  TORCH_CHECK(y.numel() == N, "y must have one entry per row");
+  TORCH_CHECK(w.dim() == 2 && w.size(0) == TB && w.size(1) == N, "w must be u8[TB, N]");
+  TORCH_CHECK(total_bins >= 1 && total_bins <= F * HGBT_MAX_BINS &&
+              n_slots * 2 * total_bins < (int64_t(1) << 31),
+              "histogram shape out of range");
+  TORCH_CHECK(rows_per_block >= 1 && rows_per_block <= HRF_MAX_ROWS_PER_BLOCK,
+              "rows_per_block must be in [1, ", HRF_MAX_ROWS_PER_BLOCK, "]");
+  TORCH_CHECK(lds_entries >= 0 &&
+              (size_t)lds_entries * sizeof(int) <= HGBT_LDS_BYTES_MAX,
+              "LDS slab larger than the CU's LDS");
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)bins.get_device());
+  auto hist = torch::zeros({n_slots, 2, total_bins},
+      torch::TensorOptions().dtype(torch::kInt64).device(bins.device()));
+  if (N == 0 || n_slots == 0) return hist;
+  const int64_t row_blocks = (N + rows_per_block - 1) / rows_per_block;
+  TORCH_CHECK(row_blocks < (int64_t(1) << 31), "too many rows");
+
+  static bool lds_opt_in = false;
+  if (!lds_opt_in) {  // dynamic LDS above 64 KiB needs the opt-in once
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&hrf_hist_kernel),
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)HGBT_LDS_BYTES_MAX));
+    lds_opt_in = true;
+  }
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(hrf_hist_kernel,
+      dim3((unsigned)row_blocks, (unsigned)(grp_off.size(0) - 1), (unsigned)TB),
+      dim3(HGBT_BLOCK), (size_t)lds_entries * sizeof(int), stream,
+      bins.data_ptr<uint8_t>(), bin_off.data_ptr<int>(), grp_off.data_ptr<int>(),
+      y.data_ptr<uint8_t>(), w.data_ptr<uint8_t>(), node.data_ptr<int>(),
+      slot_off.data_ptr<int>(),
+      (long long)N, (int)F, (int)n_slots, (int)total_bins, (int)rows_per_block,
+      (int)lds_entries,
+      reinterpret_cast<unsigned long long*>(hist.data_ptr<int64_t>()));
+  HIP_CHECK(hipGetLastError());
+  return hist;
+}
+
+// Chosen split per open slot: i64[n_slots, HRF_REC] records. seed is the
+// 64-bit key seed, passed as its two's-complement int64.
+torch::Tensor hrf_split(torch::Tensor hist, torch::Tensor bin_off,
+                        torch::Tensor slot_meta, int64_t max_features,
+                        int64_t min_leaf, int64_t seed)
+{
+  TORCH_CHECK(hist.is_cuda() && hist.scalar_type() == torch::kInt64 &&
+              hist.dim() == 3 && hist.size(1) == 2 && hist.is_contiguous(),
+              "hist must be a contiguous i64[n_slots, 2, total_bins] GPU tensor");
+  hgbt_check(bin_off, hist, torch::kInt32, "bin_off");
+  hgbt_check(slot_meta, hist, torch::kInt32, "slot_meta");
+  const int64_t K = hist.size(0), F = bin_off.numel() - 1;
+  TORCH_CHECK(bin_off.dim() == 1 && F >= 1 && F <= HRF_MAX_FEATS,
+              "bin_off must be i32[F+1] with F in 1..", HRF_MAX_FEATS);
+  TORCH_CHECK(slot_meta.dim() == 2 && slot_meta.size(0) == K && slot_meta.size(1) == 2,
+              "slot_meta must be i32[n_slots, 2]");
+  TORCH_CHECK(max_features >= 1 && max_features <= F, "max_features must be in [1, F]");
+  TORCH_CHECK(min_leaf >= 1, "min_leaf must be >= 1");
+  c10::hip::HIPGuard guard((c10::DeviceIndex)hist.get_device());
+  auto out = torch::zeros({K, HRF_REC},
+      torch::TensorOptions().dtype(torch::kInt64).device(hist.device()));
+  if (K == 0) return out;
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(hrf_split_kernel, dim3((unsigned)K), dim3(HGBT_BLOCK), 0, stream,
+      reinterpret_cast<const long long*>(hist.data_ptr<int64_t>()),
+      bin_off.data_ptr<int>(), slot_meta.data_ptr<int>(), (int)F, (int)hist.size(2),
+      (int)max_features, (long long)min_leaf, (unsigned long long)seed,
+      reinterpret_cast<long long*>(out.data_ptr<int64_t>()));
+  HIP_CHECK(hipGetLastError());
+  return out;
+}
+
+// Move every open row of every tree to its child (in place on `node`).
+void hrf_route(torch::Tensor bins, torch::Tensor table, torch::Tensor node,
+               torch::Tensor slot_off)
+{
+  TORCH_CHECK(table.dim() == 2 && table.size(1) == 4, "table must be i32[n_slots, 4]");
+  const int64_t K = table.size(0);
+  const int64_t TB = hrf_check_batch(bins, node, slot_off, K);
+  hgbt_check(table, bins, torch::kInt32, "table");
+  const int64_t N = bins.size(1);
+  if (N == 0 || K == 0) return;
+  const int64_t blocks = (N + HGBT_BLOCK - 1) / HGBT_BLOCK;
+  TORCH_CHECK(blocks < (int64_t(1) << 31), "too many rows");
+  c10::hip::HIPGuard guard((c10::DeviceIndex)bins.get_device());
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(hrf_route_kernel, dim3((unsigned)blocks, (unsigned)TB),
+      dim3(HGBT_BLOCK), 0, stream,
+      bins.data_ptr<uint8_t>(), reinterpret_cast<const int4*>(table.data_ptr<int>()),
+      slot_off.data_ptr<int>(), (long long)N, (int)bins.size(0), (int)K,
+      node.data_ptr<int>());
+  HIP_CHECK(hipGetLastError());
+}
+
 torch::Tensor forest_ilp_bench(
     torch::Tensor codes, torch::Tensor nums,
     torch::Tensor nodes, torch::Tensor off,
@@ -3208,6 +3630,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("HGBT_SHIFT") = py::int_(HGBT_SHIFT);
   m.attr("HGBT_MAX_ROWS_PER_BLOCK") = py::int_(HGBT_MAX_ROWS_PER_BLOCK);
   m.attr("HGBT_LDS_BYTES_MAX") = py::int_(HGBT_LDS_BYTES_MAX);
+  m.def("hrf_hist", &hrf_hist,
+        "HistForest level histogram i64[n_slots,2,total_bins] of a tree batch "
+        "(gfx950)",
+        py::arg("bins"), py::arg("bin_off"), py::arg("grp_off"), py::arg("y"),
+        py::arg("w"), py::arg("node"), py::arg("slot_off"), py::arg("n_slots"),
+        py::arg("total_bins"), py::arg("lds_entries"),
+        py::arg("rows_per_block") = HRF_MAX_ROWS_PER_BLOCK);
+  m.def("hrf_split", &hrf_split,
+        "HistForest chosen split per open slot, i64[n_slots,7] records (gfx950)",
+        py::arg("hist"), py::arg("bin_off"), py::arg("slot_meta"),
+        py::arg("max_features"), py::arg("min_leaf"), py::arg("seed"));
+  m.def("hrf_route", &hrf_route,
+        "HistForest: move the rows of every tree of the batch, in place (gfx950)",
+        py::arg("bins"), py::arg("table"), py::arg("node"), py::arg("slot_off"));
+  m.attr("HRF_MAX_ROWS_PER_BLOCK") = py::int_(HRF_MAX_ROWS_PER_BLOCK);
+  m.attr("HRF_MAX_FEATS") = py::int_(HRF_MAX_FEATS);
   m.def("drift_stats", &drift_stats,
         "Per-feature drift statistics: categorical histograms + K-S D (gfx950)");
   m.def("encode_records", &encode_records,
