@@ -123,7 +123,7 @@ def _check_shap_paths(paths, n_players: int = N_CAT + N_NUM) -> None:
         raise ValueError("SHAP path table is malformed; refusing to explain")
 
 
-EXPLAIN_METHODS = ("saabas", "shap")
+EXPLAIN_METHODS = ("saabas", "shap", "interventional")
 
 
 class ScoringEngine:
@@ -136,6 +136,21 @@ class ScoringEngine:
     # forest (every path, not one per tree), and one launch has to stay
     # short on a shared GPU
     SHAP_MAX_ROWS = 1024
+    # method="interventional" (row cap: SHAP_MAX_ROWS): most background rows
+    # one call takes (the kernel's LDS mask capacity, csrc
+    # ISHAP_MAX_BACKGROUND) ...
+    ISHAP_MAX_BACKGROUND = 1024
+    # ... and most (explained row, background row) pairs of one launch; a
+    # call above it runs as several launches over row slices. Sized on the
+    # flagship forest (RF 500 x depth 16, 1.08 M leaves) with the default
+    # 256-row sample so that the longest interventional launch is no longer
+    # than 1.25 x the method="shap" launch at SHAP_MAX_ROWS, the launch
+    # length already accepted on a shared GPU: forest_shap at 1024 rows
+    # 60.5 ms, forest_ishap at 16 rows x 256 = 4096 pairs 72.5 ms (24 rows:
+    # 80.9 ms, over the 75.6 ms bound) on an MI355X,
+    # profiles/bench_results/ishap_micro.txt. A larger background override
+    # lengthens even a one-row launch (its floor grows with R).
+    ISHAP_MAX_PAIRS = 4096
 
     def __init__(
         self,
@@ -156,6 +171,10 @@ class ScoringEngine:
         self._explain_dev = None  # lazily uploaded device tensors (explain)
         self._shap = None  # lazily built (paths, base value) of method="shap"
         self._shap_dev = None  # lazily uploaded path table
+        # method="interventional": lazily imputed packed background sample,
+        # its base value, and its device copy
+        self._ishap = None
+        self._ishap_dev = None
         if device == "cuda":
             self._init_gpu()
 
@@ -252,13 +271,22 @@ class ScoringEngine:
 
     # ------------------------------------------------------- attributions
     def explain_arrays(
-        self, codes: np.ndarray, nums: np.ndarray, method: str = "saabas"
+        self,
+        codes: np.ndarray,
+        nums: np.ndarray,
+        method: str = "saabas",
+        background=None,
     ) -> dict:
         """Per-row attributions for the classifier: prediction-path (Saabas)
         contributions by default, exact path-dependent TreeSHAP values with
         ``method="shap"`` (same keys; ``base_value`` is then the SHAP base,
         the cover-weighted expectation of the model output, and the call is
-        capped at SHAP_MAX_ROWS).
+        capped at SHAP_MAX_ROWS), interventional Shapley values against a
+        background sample with ``method="interventional"`` (same keys plus
+        ``background_rows``; ``base_value`` is then the mean model output
+        over the background rows; same row cap). ``background`` is an
+        optional encoded ``(codes, nums)`` pair that replaces the packed
+        sample for that method.
 
         Returns ``contributions`` f64[B, 23] in schema.FEATURES order,
         ``base_value``, ``output_space`` ("probability" for the averaging
@@ -271,6 +299,10 @@ class ScoringEngine:
             raise ValueError(
                 f"unknown explain method {method!r}; expected one of {EXPLAIN_METHODS}"
             )
+        if method == "interventional":
+            return self._explain_ishap(codes, nums, background)
+        if background is not None:
+            raise ValueError("background= applies to method='interventional' only")
         if method == "shap":
             return self._explain_shap(codes, nums)
         if p.cls_node_value is None:
@@ -370,13 +402,7 @@ class ScoringEngine:
         # The lock covers the lazy table build/upload and the call, as for
         # the Saabas tensors; nothing here is shared with the scoring session.
         with self._explain_lock:
-            if self._shap is None:
-                from .pack import build_shap_paths
-
-                paths, base = build_shap_paths(p)
-                _check_shap_paths(paths)
-                self._shap = (paths, base)
-            paths, base = self._shap
+            paths, base = self._path_table()
             if self.device == "cuda":
                 contrib = self._shap_gpu(paths, codes, nums)
             else:
@@ -392,11 +418,25 @@ class ScoringEngine:
             "predictions": 1.0 / (1.0 + np.exp(-raw)) if log_odds else raw,
         }
 
-    def _shap_gpu(self, paths, codes: np.ndarray, nums: np.ndarray) -> np.ndarray:
-        """forest_shap on the device; the caller holds _explain_lock."""
+    def _path_table(self):
+        """(path table, SHAP base value), built and bounds-checked once; the
+        caller holds _explain_lock. A model without per-node cover gets the
+        table too (fractions 1, base NaN): the interventional pair rule never
+        reads them, and method="shap" refuses such a model before it gets
+        here."""
+        if self._shap is None:
+            from .pack import build_shap_paths
+
+            paths, base = build_shap_paths(self.packed, require_cover=False)
+            _check_shap_paths(paths)
+            self._shap = (paths, base)
+        return self._shap
+
+    def _path_table_dev(self, paths):
+        """The path table on the device, uploaded once; the caller holds
+        _explain_lock."""
         import torch
 
-        ext = self._gpu["ext"]
         dev = torch.device("cuda", self.device_index)
         m = self._shap_dev
         if m is None:
@@ -409,6 +449,116 @@ class ScoringEngine:
                 ).to(dev),
             }
             self._shap_dev = m
+        return m
+
+    def _explain_ishap(self, codes: np.ndarray, nums: np.ndarray, background) -> dict:
+        p = self.packed
+        own = background is None  # the packed sample: base value and upload cached
+        if own:
+            if p.bg_codes is None or p.bg_nums is None:
+                raise ExplainUnavailable(
+                    "model was packed without a background sample; re-train "
+                    "and re-pack it (or pass background=) to enable "
+                    "interventional attributions"
+                )
+            background = (p.bg_codes, p.bg_nums)
+        bg_codes = np.ascontiguousarray(background[0], dtype=np.int16)
+        bg_nums = np.ascontiguousarray(background[1], dtype=np.float32)
+        r = len(bg_codes)
+        if bg_codes.shape != (r, N_CAT) or bg_nums.shape != (r, N_NUM):
+            raise ValueError(
+                f"background must be (codes [R, {N_CAT}], nums [R, {N_NUM}])"
+            )
+        if not 1 <= r <= self.ISHAP_MAX_BACKGROUND:
+            raise ValueError(
+                f"the background sample must have 1..{self.ISHAP_MAX_BACKGROUND} "
+                f"rows (got {r})"
+            )
+        b = len(codes)
+        if b > self.SHAP_MAX_ROWS:
+            raise ExplainTooLarge(
+                f"explain with method='interventional' is capped at "
+                f"{self.SHAP_MAX_ROWS} rows per call (got {b})"
+            )
+        codes = np.ascontiguousarray(codes, dtype=np.int16).reshape(b, N_CAT)
+        nums = np.ascontiguousarray(nums, dtype=np.float32).reshape(b, N_NUM)
+        # One launch covers at most ISHAP_MAX_PAIRS (row, background row)
+        # pairs; a larger call goes slice by slice.
+        step = max(1, int(self.ISHAP_MAX_PAIRS) // r)
+        with self._explain_lock:
+            paths, _ = self._path_table()
+            if own and self._ishap is not None:
+                bg_imp, base = self._ishap
+            else:
+                # host f64 from the path table: the same number on CPU and
+                # GPU engines
+                bg_imp = cpu_ref.impute_nums(p, bg_nums)
+                base = cpu_ref.forest_ishap_base_cpu(p, bg_codes, bg_imp, paths=paths)
+                if own:
+                    self._ishap = (bg_imp, base)
+            if self.device == "cuda":
+                run = self._ishap_gpu(paths, bg_codes, bg_nums, own)
+            else:
+                def run(c, x):
+                    return cpu_ref.forest_ishap_cpu(
+                        p, c, cpu_ref.impute_nums(p, x), bg_codes, bg_imp, paths=paths
+                    )
+            parts = [
+                run(codes[s : s + step], nums[s : s + step]) for s in range(0, b, step)
+            ]
+        contrib = (
+            np.concatenate(parts) if parts else np.zeros((0, N_CAT + N_NUM), dtype=np.float64)
+        )
+        raw = base + contrib.sum(axis=1)
+        log_odds = int(getattr(p, "cls_kind", 0)) == 1
+        return {
+            "contributions": contrib,
+            "base_value": base,
+            "output_space": "log_odds" if log_odds else "probability",
+            "predictions": 1.0 / (1.0 + np.exp(-raw)) if log_odds else raw,
+            "background_rows": r,
+        }
+
+    def _ishap_gpu(self, paths, bg_codes: np.ndarray, bg_nums: np.ndarray, own: bool):
+        """One-launch runner of forest_ishap on the device (rows in, f64
+        values out); the caller holds _explain_lock. The packed sample's
+        device copy is kept; an override is uploaded per call."""
+        import torch
+
+        ext = self._gpu["ext"]
+        dev = torch.device("cuda", self.device_index)
+        m = self._path_table_dev(paths)
+        bg = self._ishap_dev if own else None
+        if bg is None:
+            bg = (torch.from_numpy(bg_codes).to(dev), torch.from_numpy(bg_nums).to(dev))
+            if own:
+                self._ishap_dev = bg
+
+        def run(c: np.ndarray, x: np.ndarray) -> np.ndarray:
+            with torch.cuda.device(dev):
+                out = ext.forest_ishap(
+                    torch.from_numpy(c).to(dev),
+                    torch.from_numpy(x).to(dev),
+                    bg[0],
+                    bg[1],
+                    m["leaf_value"],
+                    m["leaf_off"],
+                    m["splits"],
+                    m["medians"],
+                    int(getattr(self.packed, "cls_kind", 0)),
+                    int(self.packed.cls_n_trees),
+                )
+                return out.cpu().numpy()  # D2H copy synchronizes the stream
+
+        return run
+
+    def _shap_gpu(self, paths, codes: np.ndarray, nums: np.ndarray) -> np.ndarray:
+        """forest_shap on the device; the caller holds _explain_lock."""
+        import torch
+
+        ext = self._gpu["ext"]
+        dev = torch.device("cuda", self.device_index)
+        m = self._path_table_dev(paths)
         with torch.cuda.device(dev):
             out = ext.forest_shap(
                 torch.from_numpy(codes).to(dev),
@@ -422,10 +572,10 @@ class ScoringEngine:
             )
             return out.cpu().numpy()  # D2H copy synchronizes the stream
 
-    def explain_records(self, records, method: str = "saabas") -> dict:
+    def explain_records(self, records, method: str = "saabas", background=None) -> dict:
         """explain_arrays on a request body (list of dicts / DataFrame)."""
         codes, nums = encode_batch(records, self.packed.vocabs)
-        return self.explain_arrays(codes, nums, method=method)
+        return self.explain_arrays(codes, nums, method=method, background=background)
 
     def encode_json_body(self, body: bytes) -> tuple:
         """Parse a raw /score JSON body into (codes, nums) with the native C

@@ -228,6 +228,8 @@ class TabularDriftDetector:
         x_ref: np.ndarray,
         p_val: float = 0.05,
         categorical_idx: tuple[int, ...] = tuple(range(9)),
+        background_rows: int = 0,
+        background_seed: int = 0,
     ):
         x_ref = np.asarray(x_ref, dtype=object)
         self.p_val = float(p_val)
@@ -248,6 +250,15 @@ class TabularDriftDetector:
         self.ref_sorted: dict[int, np.ndarray] = {}
         for i in self.numeric_idx:
             self.ref_sorted[i] = np.sort(x_ref[:, i].astype(np.float64))
+        # Optional background sample for interventional attributions
+        # (/explain?method=interventional): min(n, n_ref) raw reference rows,
+        # drawn without replacement and kept in reference order.
+        if background_rows > 0:
+            rng = np.random.default_rng(background_seed)
+            idx = np.sort(
+                rng.choice(self.n_ref, size=min(int(background_rows), self.n_ref), replace=False)
+            )
+            self.background = x_ref[idx].copy()
 
     def feature_pvals(self, x: np.ndarray) -> np.ndarray:
         x = np.asarray(x, dtype=object)

@@ -249,6 +249,193 @@ def forest_shap_cpu(
     return acc * scale
 
 
+def ishap_weight_table(n: int = N_CAT + N_NUM) -> np.ndarray:
+    """W[a, b] = (a-1)! b! / (a+b)! for a >= 1 (row 0 is zero), f64[n+1, n+1]:
+    the Shapley weight of a player that is one of ``a`` players on its own
+    side of an (explained row, background row) pair with ``b`` players on the
+    other side. Built from W[a, 0] = 1/a by W[a, b] = W[a, b-1] * b / (a+b),
+    so no factorial is ever formed (23! is not exact in f64); the kernel
+    builds the same table with the same operations."""
+    w = np.zeros((n + 1, n + 1), dtype=np.float64)
+    for a in range(1, n + 1):
+        w[a, 0] = 1.0 / a
+        for b in range(1, n + 1):
+            w[a, b] = w[a, b - 1] * b / (a + b)
+    return w
+
+
+_POP16 = np.array([bin(i).count("1") for i in range(1 << 16)], dtype=np.int64)
+
+
+def _popcount32(x: np.ndarray) -> np.ndarray:
+    return _POP16[x & 0xFFFF] + _POP16[x >> 16]
+
+
+class _IshapIndex:
+    """The path table decoded once for the interventional reference: per
+    record the compare, per player group its records and its leaf."""
+
+    def __init__(self, paths):
+        from ..pack import SHAP_CODE_SHIFT, SHAP_DIR_RIGHT, SHAP_FIRST, SHAP_PLAYER_SHIFT
+
+        sp = paths.splits
+        flags = sp[:, 3].view(np.uint32).astype(np.int64)
+        self.thr = sp[:, 1].view(np.float32)
+        self.right = (flags & SHAP_DIR_RIGHT) != 0
+        self.player = (flags >> SHAP_PLAYER_SHIFT) & 0xFF
+        self.code = (flags >> SHAP_CODE_SHIFT) - 1
+        self.off = paths.leaf_off.astype(np.int64)
+        self.n_leaves = paths.n_leaves
+        self.leaf_value = paths.leaf_value.astype(np.float64)
+        self.gstart = np.flatnonzero((flags & SHAP_FIRST) != 0)
+        rec_leaf = np.repeat(np.arange(self.n_leaves), np.diff(self.off))
+        self.n_groups = np.bincount(rec_leaf[self.gstart], minlength=self.n_leaves)
+        self.leaf_goff = np.zeros(self.n_leaves + 1, dtype=np.int64)
+        np.cumsum(self.n_groups, out=self.leaf_goff[1:])
+        self.g_player = self.player[self.gstart]
+        # bit of each record's group within its leaf's mask
+        first = (flags & SHAP_FIRST) != 0
+        self.rec_bit = (
+            np.int64(1) << np.minimum(np.cumsum(first) - 1 - self.leaf_goff[rec_leaf], 31)
+        ).astype(np.uint32)
+        if self.n_leaves and int(self.n_groups.max()) > N_CAT + N_NUM:
+            raise ValueError("a leaf has more player groups than source columns")
+        self.full = ((np.int64(1) << self.n_groups) - 1).astype(np.uint32)
+
+    def masks(self, a: int, b: int, codes: np.ndarray, nums_imp: np.ndarray) -> np.ndarray:
+        """u32[b - a, N]: bit j of [l, n] is set iff row n satisfies every
+        split of player group j of leaf a + l (f32 compares, as the scorer).
+        Leaf-major, so that the per-leaf reduction runs over contiguous rows."""
+        r0, r1 = int(self.off[a]), int(self.off[b])
+        out = np.repeat(self.full[a:b, None], len(codes), axis=1)
+        if r1 == r0 or not len(codes):
+            return out
+        code, pl = self.code[r0:r1], self.player[r0:r1]
+        cat = code >= 0
+        x = np.empty((r1 - r0, len(codes)), dtype=np.float32)
+        x[cat] = codes.T[pl[cat]] == code[cat][:, None]
+        x[~cat] = nums_imp.T[pl[~cat] - N_CAT]
+        fails = (x <= self.thr[r0:r1, None]) == self.right[r0:r1, None]
+        # OR the group bit of every failed record over each leaf's records
+        ne = self.n_groups[a:b] > 0
+        failed = np.bitwise_or.reduceat(
+            fails * self.rec_bit[r0:r1, None], (self.off[a:b] - r0)[ne], axis=0
+        )
+        out[ne] &= ~failed
+        return out
+
+    def chunks(self, n_a: int, n_b: int, max_bytes: int):
+        """Leaf ranges whose temporaries (the [n_a, n_b, leaves] u32 pair
+        arrays and the per-record compares) stay under ``max_bytes``."""
+        depth = max(1.0, float(self.off[-1]) / max(1, self.n_leaves))
+        per_leaf = 12 * max(1, n_a) * n_b + 16 * (n_a + n_b) * depth
+        step = max(1, int(max_bytes // per_leaf))
+        for a in range(0, self.n_leaves, step):
+            yield a, min(a + step, self.n_leaves)
+
+
+def _ishap_scale(packed: PackedModel) -> float:
+    T = len(packed.cls_tree_offsets) - 1
+    return 1.0 if getattr(packed, "cls_kind", 0) == 1 else 1.0 / T
+
+
+def _ishap_paths(packed: PackedModel, paths):
+    if paths is None:
+        from ..pack import build_shap_paths
+
+        paths, _ = build_shap_paths(packed, require_cover=False)
+    return paths
+
+
+def forest_ishap_cpu(
+    packed: PackedModel,
+    codes: np.ndarray,
+    nums_imp: np.ndarray,
+    bg_codes: np.ndarray,
+    bg_nums_imp: np.ndarray,
+    paths=None,
+    max_bytes: int = 64 << 20,
+) -> np.ndarray:
+    """Interventional Shapley values against a background sample,
+    f64[B, N_CAT + N_NUM] in schema feature order (one-hot features fold onto
+    their categorical column). The game: val(S) = mean over background rows r
+    of f(hybrid row: x on the columns of S, r elsewhere).
+
+    Closed form per (x, r, leaf) with value v: a_p / b_p = 1 iff x / r
+    satisfies every split of player p on the leaf's path. The pair reaches
+    the leaf for some coalition iff a_p | b_p for every p; then with
+    X = {a & !b}, R = {!a & b}, nx = |X|, nr = |R|, each i in X gets
+    +v (nx-1)! nr! / (nx+nr)! and each i in R gets -v (nr-1)! nx! / (nx+nr)!
+    (players with a & b are dummies of the pair). Summed over leaves,
+    averaged over r, scaled by 1/T for the averaging forests and 1 for
+    gradient boosting, so that forest_ishap_base_cpu plus the row sum is the
+    model output. Same f32 compares as score_forest_cpu; the rest is f64.
+    ``paths`` takes a prebuilt table; ``frac`` is never read, so a table
+    built without cover serves. Leaves go in chunks under ``max_bytes``."""
+    ix = _IshapIndex(_ishap_paths(packed, paths))
+    codes, bg_codes = np.asarray(codes), np.asarray(bg_codes)
+    n_rows, n_bg = len(codes), len(bg_codes)
+    if n_bg < 1:
+        raise ValueError("the background sample is empty")
+    n_src = N_CAT + N_NUM
+    acc = np.zeros(n_rows * n_src, dtype=np.float64)
+    if n_rows == 0 or ix.off[-1] == 0:
+        return acc.reshape(n_rows, n_src)
+    w_tab = ishap_weight_table()
+    for a, b in ix.chunks(n_rows, n_bg, max_bytes):
+        am = ix.masks(a, b, codes, nums_imp)
+        bm = ix.masks(a, b, bg_codes, bg_nums_imp)
+        live = (am[:, :, None] | bm[:, None, :]) == ix.full[a:b, None, None]
+        li, xi, ri = np.nonzero(live)
+        ma, mb = am[li, xi], bm[li, ri]
+        mx, mr = ma & ~mb, mb & ~ma  # players only x / only r satisfies
+        keep = (mx | mr) != 0
+        xi, li, mx, mr = xi[keep], li[keep], mx[keep], mr[keep]
+        if not len(xi):
+            continue
+        nx, nr = _popcount32(mx), _popcount32(mr)
+        v = ix.leaf_value[a + li]
+        wp, wn = v * w_tab[nx, nr], v * w_tab[nr, nx]
+        gbase = ix.leaf_goff[a + li]
+        for j in range(int(ix.n_groups[a:b].max())):
+            sx, sr = (mx >> j) & 1 != 0, (mr >> j) & 1 != 0
+            sel = sx | sr
+            if not sel.any():
+                continue
+            player = ix.g_player[gbase[sel] + j]
+            acc += np.bincount(
+                xi[sel] * n_src + player,
+                weights=np.where(sx[sel], wp[sel], -wn[sel]),
+                minlength=len(acc),
+            )
+    return acc.reshape(n_rows, n_src) * _ishap_scale(packed) / n_bg
+
+
+def forest_ishap_base_cpu(
+    packed: PackedModel,
+    bg_codes: np.ndarray,
+    bg_nums_imp: np.ndarray,
+    paths=None,
+    max_bytes: int = 64 << 20,
+) -> float:
+    """Base value of the interventional game: the f64 mean over the
+    background rows of the raw model output (probability, or log-odds for
+    gradient boosting), from the same path table as forest_ishap_cpu — a row
+    lands in the leaf whose every player group it satisfies."""
+    ix = _IshapIndex(_ishap_paths(packed, paths))
+    bg_codes = np.asarray(bg_codes)
+    if len(bg_codes) < 1:
+        raise ValueError("the background sample is empty")
+    total = np.zeros(len(bg_codes), dtype=np.float64)
+    for a, b in ix.chunks(0, len(bg_codes), max_bytes):
+        hit = ix.masks(a, b, bg_codes, bg_nums_imp) == ix.full[a:b, None]
+        total += ix.leaf_value[a:b] @ hit
+    raw = total * _ishap_scale(packed)
+    if getattr(packed, "cls_kind", 0) == 1:
+        raw = raw + float(packed.cls_bias)
+    return float(raw.mean())
+
+
 def score_iforest_cpu(
     packed: PackedModel, nums_imp: np.ndarray
 ) -> tuple[np.ndarray, np.ndarray]:

@@ -218,6 +218,10 @@ class PackedModel:
     # optional per-node cover (training weight that reached the node),
     # index-aligned with cls_nodes: what exact TreeSHAP needs on top
     cls_node_cover: np.ndarray | None = None  # f32[n_nodes]
+    # optional background sample of interventional attributions: encoded
+    # reference rows (NaNs kept; imputed where rows are imputed)
+    bg_codes: np.ndarray | None = None  # i16[R, N_CAT]
+    bg_nums: np.ndarray | None = None  # f32[R, N_NUM]
 
     meta: dict = field(default_factory=dict)
 
@@ -241,6 +245,9 @@ class PackedModel:
             extra["cls_base_value"] = self.cls_base_value
         if self.cls_node_cover is not None:
             extra["cls_node_cover"] = self.cls_node_cover
+        if self.bg_codes is not None and self.bg_nums is not None:
+            extra["bg_codes"] = self.bg_codes
+            extra["bg_nums"] = self.bg_nums
         np.savez_compressed(
             path,
             **extra,
@@ -303,6 +310,8 @@ class PackedModel:
                 float(z["cls_base_value"]) if "cls_base_value" in z else 0.0
             ),
             cls_node_cover=z["cls_node_cover"] if "cls_node_cover" in z else None,
+            bg_codes=z["bg_codes"] if "bg_codes" in z and "bg_nums" in z else None,
+            bg_nums=z["bg_nums"] if "bg_codes" in z and "bg_nums" in z else None,
         )
 
 
@@ -447,22 +456,31 @@ class ShapPaths:
         return len(self.leaf_value)
 
 
-def build_shap_paths(packed: "PackedModel") -> tuple[ShapPaths, float]:
+def build_shap_paths(
+    packed: "PackedModel", require_cover: bool = True
+) -> tuple[ShapPaths, float]:
     """Path table for exact path-dependent TreeSHAP and the SHAP base value.
 
     The base value is the cover-weighted expectation of the model output,
     sum_leaves v * prod_path frac under the forest's scaling (1/T for the
     averaging forests; 1 plus cls_bias for gradient boosting), in f64 over
     the same f32 ``frac`` values the table stores. Vectorised over all nodes:
-    the only Python loops run over tree levels."""
-    if packed.cls_node_cover is None:
-        raise ValueError(
-            "model was packed without per-node cover (cls_node_cover is None); "
-            "re-pack it to compute SHAP values"
-        )
+    the only Python loops run over tree levels.
+
+    ``require_cover=False`` also accepts a model packed without per-node
+    cover, for the interventional game, whose pair rule never reads ``frac``:
+    every ``frac`` is then 1 and the returned base value is NaN."""
     nodes = np.asarray(packed.cls_nodes)
+    if packed.cls_node_cover is None:
+        if require_cover:
+            raise ValueError(
+                "model was packed without per-node cover (cls_node_cover is None); "
+                "re-pack it to compute SHAP values"
+            )
+        cover = np.ones(len(nodes), dtype=np.float64)
+    else:
+        cover = np.asarray(packed.cls_node_cover, dtype=np.float64)
     off = np.asarray(packed.cls_tree_offsets, dtype=np.int64)
-    cover = np.asarray(packed.cls_node_cover, dtype=np.float64)
     n = len(nodes)
     if cover.shape != (n,):
         raise ValueError("cls_node_cover is not aligned with cls_nodes")
@@ -553,7 +571,9 @@ def build_shap_paths(packed: "PackedModel") -> tuple[ShapPaths, float]:
     splits[:, 3] = flags.astype(np.uint32).view(np.int32)
 
     total = float((leaf_value.astype(np.float64) * reach[leaves]).sum())
-    if int(getattr(packed, "cls_kind", 0)) == 1:
+    if packed.cls_node_cover is None:
+        base_value = float("nan")  # no cover, no path-dependent expectation
+    elif int(getattr(packed, "cls_kind", 0)) == 1:
         base_value = float(packed.cls_bias) + total
     else:
         base_value = total / (len(off) - 1)
@@ -625,7 +645,10 @@ def pack_drift(detector, vocabs: list[list[str]]) -> dict:
         cat_counts.append(counts)
         cat_off[j + 1] = cat_off[j] + len(counts)
 
+    bg_codes, bg_nums = encode_background(getattr(detector, "background", None), vocabs)
     return {
+        "bg_codes": bg_codes,
+        "bg_nums": bg_nums,
         "n_ref": int(detector.n_ref),
         "drift_p_val": float(detector.p_val),
         "ref_sorted": np.concatenate(ref_sorted),
@@ -633,6 +656,29 @@ def pack_drift(detector, vocabs: list[list[str]]) -> dict:
         "ref_cat_counts": np.concatenate(cat_counts),
         "ref_cat_offsets": cat_off,
     }
+
+
+def encode_background(rows, vocabs: list[list[str]]):
+    """Encode a detector's background sample (raw objects, schema.FEATURES
+    column order) with the request encoder: (i16[R, N_CAT], f32[R, N_NUM]),
+    NaNs kept. (None, None) without a sample."""
+    if rows is None or len(rows) == 0:
+        return None, None
+    n_cat = len(CATEGORICAL_FEATURES)
+    recs = []
+    for row in np.asarray(rows, dtype=object):
+        rec = {
+            c: MISSING_CATEGORY if v is None or v != v else str(v)
+            for c, v in zip(CATEGORICAL_FEATURES, row[:n_cat])
+        }
+        for c, v in zip(NUMERIC_FEATURES, row[n_cat:]):
+            rec[c] = float("nan") if v is None else float(v)
+        recs.append(rec)
+    codes, nums = encode_batch(recs, vocabs)
+    return (
+        np.ascontiguousarray(codes, dtype=np.int16),
+        np.ascontiguousarray(nums, dtype=np.float32),
+    )
 
 
 def pack_pyfunc_dir(model_dir: str) -> PackedModel:

@@ -93,6 +93,11 @@ def broadcast_packed(
         meta["has_node_cover"] = packed.cls_node_cover is not None
         if meta["has_node_cover"]:
             meta["node_cover_shape"] = list(packed.cls_node_cover.shape)
+        meta["has_background"] = (
+            packed.bg_codes is not None and packed.bg_nums is not None
+        )
+        if meta["has_background"]:
+            meta["bg_rows"] = int(len(packed.bg_codes))
         obj = [meta]
     else:
         obj = [None]
@@ -148,6 +153,26 @@ def broadcast_packed(
         dist.broadcast(nc, src=src, group=group)
         cls_node_cover = nc.cpu().numpy()
 
+    # optional background sample (interventional attributions): i16 codes
+    # and f32 numerics, NaNs included, bit for bit
+    bg_codes = bg_nums = None
+    if meta["has_background"]:
+        r = meta["bg_rows"]
+        if is_src:
+            bc = torch.from_numpy(
+                np.ascontiguousarray(packed.bg_codes.astype(np.int16, copy=False))
+            ).to(device)
+            bn = torch.from_numpy(
+                np.ascontiguousarray(packed.bg_nums.astype(np.float32, copy=False))
+            ).to(device)
+        else:
+            bc = torch.empty((r, N_CAT), dtype=torch.int16, device=device)
+            bn = torch.empty((r, N_NUM), dtype=torch.float32, device=device)
+        # int16 is no collective dtype on RCCL: the codes travel as bytes
+        dist.broadcast(bc.view(torch.uint8), src=src, group=group)
+        dist.broadcast(bn, src=src, group=group)
+        bg_codes, bg_nums = bc.cpu().numpy(), bn.cpu().numpy()
+
     if is_src:
         return packed
     kw = {name: tensors[name].cpu().numpy() for name, _ in _ARRAY_FIELDS}
@@ -159,6 +184,8 @@ def broadcast_packed(
         cls_node_value=cls_node_value,
         cls_base_value=meta.get("cls_base_value", 0.0),
         cls_node_cover=cls_node_cover,
+        bg_codes=bg_codes,
+        bg_nums=bg_nums,
         meta=meta["meta"],
         **kw,
     )

@@ -134,7 +134,11 @@ class ExplainOutput(BaseModel):
     by default or exact TreeSHAP values with ``?method=shap``.
     base_value + sum(contributions[r]) is the model output for row r in
     ``output_space`` ("probability", or "log_odds" for gradient boosting).
-    ``method`` echoes the query parameter and is absent when none was given."""
+    ``method`` echoes the query parameter and is absent when none was given.
+    ``?method=interventional`` gives Shapley values of the interventional
+    game against the model's background sample; ``base_value`` is then the
+    mean model output over those rows and ``background_rows`` their number
+    (absent for the other methods)."""
 
     output_space: str
     base_value: float
@@ -143,6 +147,7 @@ class ExplainOutput(BaseModel):
     contributions: list[list[float]]
     top_reasons: list[list[Reason]]
     method: str | None = None
+    background_rows: int | None = None
 
 
 # The one-record CI smoke-test fixture (reference app/sample-request.json).

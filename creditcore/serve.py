@@ -519,7 +519,9 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
     ):
         """Per-row feature attributions ("reason codes") for the classifier:
         prediction-path (Saabas) contributions per input feature by default,
-        exact TreeSHAP values with ``?method=shap``, plus the up-to-top_k
+        exact TreeSHAP values with ``?method=shap``, interventional Shapley
+        values against the model's background sample with
+        ``?method=interventional``, plus the up-to-top_k
         features pushing each row toward default. One attempt on one live
         replica; bypasses the micro-batcher."""
         import asyncio
@@ -543,7 +545,9 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
         if len(codes) == 0:
             raise HTTPException(status_code=400, detail="empty request batch")
         max_rows = (
-            ScoringEngine.SHAP_MAX_ROWS if use == "shap" else ScoringEngine.EXPLAIN_MAX_ROWS
+            ScoringEngine.SHAP_MAX_ROWS
+            if use in ("shap", "interventional")
+            else ScoringEngine.EXPLAIN_MAX_ROWS
         )
         if len(codes) > max_rows:
             raise HTTPException(
@@ -555,6 +559,14 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
                 status_code=501,
                 detail="the served model was packed without per-node cover; "
                 "re-pack it to enable /explain?method=shap",
+            )
+        if use == "interventional" and (
+            engines[0].packed.bg_codes is None or engines[0].packed.bg_nums is None
+        ):
+            raise HTTPException(
+                status_code=501,
+                detail="the served model was packed without a background sample; "
+                "re-train and re-pack it to enable /explain?method=interventional",
             )
         if use == "saabas" and engines[0].packed.cls_node_value is None:
             raise HTTPException(
@@ -590,6 +602,8 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
         }
         if method is not None:  # a default request keeps its key set
             payload["method"] = method
+        if "background_rows" in out:  # method=interventional only
+            payload["background_rows"] = int(out["background_rows"])
         metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
         return _json_response(payload)
 

@@ -46,6 +46,8 @@ from .models.iforest import IForestDetector
 from .schema import CATEGORICAL_FEATURES, FEATURES, INPUT_SAMPLE, NUMERIC_FEATURES, TARGET
 
 DEFAULT_MODEL_NAME = "credit-default-uci-custom"  # reference 02-register cell-13
+# reference rows kept as the background sample of interventional attributions
+BACKGROUND_ROWS = 256
 
 
 class QualityGateError(RuntimeError):
@@ -161,6 +163,7 @@ def fit_detectors(df: pd.DataFrame) -> tuple[TabularDriftDetector, IForestDetect
         df[FEATURES].values,
         p_val=0.05,
         categorical_idx=tuple(range(len(CATEGORICAL_FEATURES))),
+        background_rows=BACKGROUND_ROWS,
     )
     outlier = IForestDetector(threshold=0.95)
     outlier.fit(df[NUMERIC_FEATURES].values.astype(np.float64))

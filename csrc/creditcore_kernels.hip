@@ -548,6 +548,196 @@ __global__ __launch_bounds__(CONTRIB_BLOCK) void forest_shap_kernel(
   }
 }
 
+// Interventional Shapley values against a background sample, over the same
+// path table (frac is not read). The game for explained row x and background
+// row r: a coalition's hybrid row takes x on its columns and r elsewhere;
+// values are averaged over r. Closed form per (x, r, leaf) with leaf value v:
+// a_p / b_p = 1 iff x / r satisfies every split of player group p of the
+// path. The pair can reach the leaf only if a_p | b_p for every p. Then with
+// X = a & ~b, R = ~a & b, nx = |X|, nr = |R|:
+//   each i in X gets +v (nx-1)! nr! / (nx+nr)!,
+//   each i in R gets -v (nr-1)! nx! / (nx+nr)!,
+// and players with a_p & b_p are dummies of the pair. With the masks as
+// <= 23-bit words the pair step is one compare, two popcounts and two reads
+// of ISHAP_W[a][b] = (a-1)! b! / (a+b)!.
+//
+// forest_shap_kernel's skeleton: one thread per explained row, CONTRIB_BLOCK
+// rows staged column-major in LDS with fused imputation, N_SRC f64
+// accumulators per thread in LDS, blockIdx.y strides over paths, all loops
+// with block-uniform trip counts (threads past n_rows stay in the barriers
+// on a clamped row and only skip the flush). Per path:
+//   1. every thread walks the records for its own row -> a; the walk also
+//      yields the group -> player map (thread 0 writes it to LDS);
+//   2. the block walks the records for the background rows, thread j taking
+//      rows j, j + CONTRIB_BLOCK, ... (row-major reads of arrays of at most
+//      76 KB that stay in L2, imputation fused) -> one u32 mask per
+//      background row in LDS; nothing per (path, background row) goes to HBM;
+//   3. barrier; every thread loops over the LDS masks (broadcast reads),
+//      skips dead pairs and credits the set bits of X and R;
+//   4. barrier (the masks and the map are rewritten by the next path).
+// The records are walked (rows + background) x depth per path, not per pair.
+// LDS: 33,024 B as forest_contrib_kernel + 4,096 B masks + 4,608 B weight
+// table + 92 B group -> player map = 41,820 B static (three blocks per CU).
+#define ISHAP_MAX_BACKGROUND 1024
+static_assert(N_SRC < 32, "player-group masks are 32-bit words");
+
+// ISHAP_W[a][b] = (a-1)! b! / (a+b)!, a >= 1, from W[a][0] = 1/a and
+// W[a][b] = W[a][b-1] * b / (a+b): ratios only, no factorial is formed
+// (23! is not exact in f64). cpu_ref.ishap_weight_table does the same.
+struct IshapWeights {
+  double w[N_SRC + 1][N_SRC + 1];
+  constexpr IshapWeights() : w{} {
+    for (int a = 1; a <= N_SRC; ++a) {
+      w[a][0] = 1.0 / (double)a;
+      for (int b = 1; b <= N_SRC; ++b)
+        w[a][b] = w[a][b - 1] * (double)b / (double)(a + b);
+    }
+  }
+};
+__constant__ IshapWeights ISHAP_W = IshapWeights();
+
+__global__ __launch_bounds__(CONTRIB_BLOCK) void forest_ishap_kernel(
+    const short* __restrict__ codes,       // [B, N_CAT]
+    const float* __restrict__ nums,        // [B, N_NUM]
+    const short* __restrict__ bg_codes,    // [R, N_CAT]
+    const float* __restrict__ bg_nums,     // [R, N_NUM], NaNs not yet imputed
+    const float* __restrict__ medians,     // [N_NUM]
+    const float* __restrict__ leaf_value,  // [L]
+    const int* __restrict__ leaf_off,      // [L+1] into splits
+    const int4* __restrict__ splits,       // [S] {feat, thr bits, frac bits, flags}
+    int n_leaves,
+    int n_rows,
+    int n_bg,                              // 1 <= R <= ISHAP_MAX_BACKGROUND (host)
+    double scale_over_r,                   // (1/T or 1) / R
+    double* __restrict__ phi)              // [B, N_SRC], pre-zeroed
+{
+  __shared__ double s_acc[N_SRC * CONTRIB_BLOCK];
+  __shared__ short s_codes[N_CAT * CONTRIB_BLOCK];
+  __shared__ float s_nums[N_NUM * CONTRIB_BLOCK];
+  __shared__ unsigned s_mask[ISHAP_MAX_BACKGROUND];
+  __shared__ double s_w[(N_SRC + 1) * (N_SRC + 1)];
+  __shared__ int s_player[N_SRC];  // player of each group of the current path
+
+  const int tid = threadIdx.x;
+  const int row_raw = blockIdx.x * CONTRIB_BLOCK + tid;
+  const bool live = row_raw < n_rows;
+  const int row = live ? row_raw : n_rows - 1;  // n_rows >= 1 (host)
+
+#pragma unroll
+  for (int c = 0; c < N_CAT; ++c)
+    s_codes[c * CONTRIB_BLOCK + tid] = codes[(size_t)row * N_CAT + c];
+#pragma unroll
+  for (int c = 0; c < N_NUM; ++c) {
+    const float v = nums[(size_t)row * N_NUM + c];
+    s_nums[c * CONTRIB_BLOCK + tid] = isnan(v) ? medians[c] : v;
+  }
+#pragma unroll
+  for (int c = 0; c < N_SRC; ++c) s_acc[c * CONTRIB_BLOCK + tid] = 0.0;
+  for (int j = tid; j < (N_SRC + 1) * (N_SRC + 1); j += CONTRIB_BLOCK)
+    s_w[j] = ISHAP_W.w[j / (N_SRC + 1)][j % (N_SRC + 1)];
+  // the first barrier of the path loop orders s_w before its first read; a
+  // block whose paths are all skipped never reads it
+
+  for (int leaf = blockIdx.y; leaf < n_leaves; leaf += gridDim.y) {
+    const int r0 = leaf_off[leaf];
+    const int r1 = leaf_off[leaf + 1];
+    if (r1 == r0) continue;  // root leaf: no players (block-uniform)
+
+    // 1. the own row's mask, the group count and the group -> player map
+    unsigned a = 0;
+    int m = 0;  // player groups closed so far
+    bool o = true;
+    for (int r = r0; r < r1; ++r) {
+      const int4 rec = splits[r];
+      const int player = (rec.w >> SHAP_PLAYER_SHIFT) & 0xFF;
+      const int code = (int)((unsigned)rec.w >> SHAP_CODE_SHIFT) - 1;
+      const float x =
+          (code >= 0) ? ((s_codes[player * CONTRIB_BLOCK + tid] == (short)code) ? 1.0f : 0.0f)
+                      : s_nums[(player - N_CAT) * CONTRIB_BLOCK + tid];
+      const bool right = !(x <= __int_as_float(rec.y));
+      o = o && (right == (bool)(rec.w & SHAP_DIR_RIGHT));
+      const bool last = (r + 1 == r1) || (splits[r + 1].w & SHAP_FIRST);
+      if (last) {  // block-uniform
+        if (m < N_SRC) {
+          a |= (o ? 1u : 0u) << m;
+          if (tid == 0) s_player[m] = player;
+        }
+        ++m;
+        o = true;
+      }
+    }
+    // The host has checked the table (at most N_SRC groups per path); a
+    // path that breaks that is skipped, never indexed (block-uniform, and
+    // before this iteration's barriers).
+    if (m > N_SRC) continue;
+    const unsigned full = (1u << m) - 1u;
+
+    // 2. one mask per background row
+    for (int k = tid; k < n_bg; k += CONTRIB_BLOCK) {
+      const short* bc = bg_codes + (size_t)k * N_CAT;
+      const float* bn = bg_nums + (size_t)k * N_NUM;
+      unsigned b = 0;
+      int g = 0;
+      bool ob = true;
+      for (int r = r0; r < r1; ++r) {
+        const int4 rec = splits[r];
+        const int player = (rec.w >> SHAP_PLAYER_SHIFT) & 0xFF;
+        const int code = (int)((unsigned)rec.w >> SHAP_CODE_SHIFT) - 1;
+        float x;
+        if (code >= 0) {
+          x = (bc[player] == (short)code) ? 1.0f : 0.0f;
+        } else {
+          x = bn[player - N_CAT];
+          if (isnan(x)) x = medians[player - N_CAT];
+        }
+        const bool right = !(x <= __int_as_float(rec.y));
+        ob = ob && (right == (bool)(rec.w & SHAP_DIR_RIGHT));
+        const bool last = (r + 1 == r1) || (splits[r + 1].w & SHAP_FIRST);
+        if (last) {
+          b |= (ob ? 1u : 0u) << g;
+          ++g;
+          ob = true;
+        }
+      }
+      s_mask[k] = b;
+    }
+    __syncthreads();  // masks, s_player (and s_w on the first path) complete
+
+    // 3. the pairs of this thread's row
+    const double v = (double)leaf_value[leaf];
+    for (int k = 0; k < n_bg; ++k) {
+      const unsigned b = s_mask[k];
+      if ((a | b) != full) continue;  // no coalition reaches the leaf
+      unsigned mx = a & ~b;
+      unsigned mr = b & ~a;
+      if ((mx | mr) == 0u) continue;  // every player a dummy of the pair
+      const int nx = __popc(mx);
+      const int nr = __popc(mr);
+      const double wp = v * s_w[nx * (N_SRC + 1) + nr];
+      const double wn = v * s_w[nr * (N_SRC + 1) + nx];
+      while (mx) {
+        const int g = __ffs((int)mx) - 1;
+        mx &= mx - 1u;
+        s_acc[s_player[g] * CONTRIB_BLOCK + tid] += wp;
+      }
+      while (mr) {
+        const int g = __ffs((int)mr) - 1;
+        mr &= mr - 1u;
+        s_acc[s_player[g] * CONTRIB_BLOCK + tid] -= wn;
+      }
+    }
+    __syncthreads();  // the next path rewrites s_mask and s_player
+  }
+
+  if (!live) return;
+  double* out = phi + (size_t)row * N_SRC;
+#pragma unroll
+  for (int c = 0; c < N_SRC; ++c) {
+    const double acc = s_acc[c * CONTRIB_BLOCK + tid];
+    if (acc != 0.0) atomicAdd(&out[c], acc * scale_over_r);
+  }
+}
+
 // 4-tree ILP + optional transposed grid (blockIdx.x = tree chunk so the
 // dispatcher's id%8 XCD placement gives adjacent chunks to different XCDs,
 // keeping each XCD's L2 on a tree subset). Experimental A/B variants.
@@ -1186,6 +1376,71 @@ torch::Tensor forest_shap(
       shap.data_ptr<double>());
   HIP_CHECK(hipGetLastError());
   return shap;
+}
+
+// Interventional Shapley values f64[B, 23] of the classifier forest against
+// the background rows (forest_ishap_kernel), from the same path table.
+// Stateless like forest_shap; the caller has bounds-checked the table
+// (engine._check_shap_paths: record players, at most N_SRC groups per path).
+torch::Tensor forest_ishap(
+    torch::Tensor codes, torch::Tensor nums,
+    torch::Tensor bg_codes, torch::Tensor bg_nums,
+    torch::Tensor leaf_value, torch::Tensor leaf_off, torch::Tensor splits,
+    torch::Tensor medians, int64_t cls_kind, int64_t n_trees,
+    int64_t block_target)
+{
+  check_inputs(codes, nums);
+  TORCH_CHECK(block_target >= 1 && block_target <= 65535, "bad block_target");
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType st, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == codes.device(), name,
+                " must be on the inputs' GPU");
+    TORCH_CHECK(t.scalar_type() == st && t.is_contiguous(), name,
+                " has the wrong dtype or is not contiguous");
+  };
+  on_dev(nums, torch::kFloat32, "nums");
+  on_dev(bg_codes, torch::kInt16, "bg_codes");
+  on_dev(bg_nums, torch::kFloat32, "bg_nums");
+  on_dev(leaf_value, torch::kFloat32, "leaf_value");
+  on_dev(leaf_off, torch::kInt32, "leaf_off");
+  on_dev(splits, torch::kInt32, "splits");
+  on_dev(medians, torch::kFloat32, "medians");
+  TORCH_CHECK(bg_codes.dim() == 2 && bg_codes.size(1) == N_CAT,
+              "bg_codes must be [R, N_CAT]");
+  TORCH_CHECK(bg_nums.dim() == 2 && bg_nums.size(1) == N_NUM &&
+              bg_nums.size(0) == bg_codes.size(0),
+              "bg_nums must be [R, N_NUM] with bg_codes' R");
+  TORCH_CHECK(bg_codes.size(0) >= 1 && bg_codes.size(0) <= ISHAP_MAX_BACKGROUND,
+              "the background sample must have 1..", ISHAP_MAX_BACKGROUND, " rows");
+  TORCH_CHECK(leaf_value.dim() == 1 && leaf_off.dim() == 1 &&
+              leaf_off.size(0) == leaf_value.size(0) + 1,
+              "leaf_off must have one entry more than leaf_value");
+  TORCH_CHECK(splits.dim() == 2 && splits.size(1) == 4, "splits must be [S, 4]");
+  TORCH_CHECK(medians.numel() == N_NUM, "medians must have N_NUM entries");
+  TORCH_CHECK(n_trees >= 1, "forest has no trees");
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)codes.get_device());
+  const int B = (int)codes.size(0);
+  const int R = (int)bg_codes.size(0);
+  const int L = (int)leaf_value.size(0);
+  auto phi = torch::zeros({B, N_SRC},
+      torch::TensorOptions().dtype(torch::kFloat64).device(codes.device()));
+  if (B == 0 || L == 0) return phi;
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  const int row_blocks = ceil_div(B, CONTRIB_BLOCK);
+  // forest_shap's grid rule: path-chunks fill the CUs at small B
+  const int chunks = std::max(1, std::min(ceil_div((int)block_target, row_blocks), L));
+  const double scale = (cls_kind == 1) ? 1.0 : 1.0 / (double)n_trees;
+  hipLaunchKernelGGL(forest_ishap_kernel, dim3(row_blocks, chunks),
+      dim3(CONTRIB_BLOCK), 0, stream,
+      codes.data_ptr<short>(), nums.data_ptr<float>(),
+      bg_codes.data_ptr<short>(), bg_nums.data_ptr<float>(),
+      medians.data_ptr<float>(),
+      leaf_value.data_ptr<float>(), leaf_off.data_ptr<int>(),
+      reinterpret_cast<const int4*>(splits.data_ptr<int>()), L, B, R,
+      scale / (double)R, phi.data_ptr<double>());
+  HIP_CHECK(hipGetLastError());
+  return phi;
 }
 
 // ---------------------------------------------------------------------------
@@ -3614,6 +3869,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("leaf_off"), py::arg("splits"), py::arg("medians"),
         py::arg("cls_kind"), py::arg("n_trees"),
         py::arg("block_target") = 2048);
+  m.def("forest_ishap", &forest_ishap,
+        "Per-row interventional Shapley values f64[B,23] against a "
+        "background sample (gfx950)",
+        py::arg("codes"), py::arg("nums"), py::arg("bg_codes"),
+        py::arg("bg_nums"), py::arg("leaf_value"), py::arg("leaf_off"),
+        py::arg("splits"), py::arg("medians"), py::arg("cls_kind"),
+        py::arg("n_trees"), py::arg("block_target") = 2048);
+  m.attr("ISHAP_MAX_BACKGROUND") = py::int_(ISHAP_MAX_BACKGROUND);
   m.def("hgbt_hist", &hgbt_hist,
         "HistGBT level histogram i64[n_nodes,3,total_bins] of int32 "
         "fixed-point gradients (gfx950)",
