@@ -3,6 +3,7 @@
     python bench/train_micro.py --rows 20000
     python bench/train_micro.py --rows 1000000 --skip-exact-gbt
     python bench/train_micro.py --mode forest --rows 20000 --depth 8
+    python bench/train_micro.py --rows 20000 --monotone 3 --skip-exact-gbt
 
 Every estimator gets the same preprocessed matrix (the pipeline's
 [one-hot | 14 numerics] feature space, dense f32), the same 80/20 split and
@@ -10,7 +11,10 @@ the same n_estimators / max_depth / learning_rate. Prints one JSON line per
 estimator with the fit wall time (host binning and transfers included for
 hgbt) and the held-out log-loss, then one summary line. sklearn's exact
 GradientBoostingClassifier is single-threaded; --skip-exact-gbt leaves it out
-at row counts where it would run for many minutes.
+at row counts where it would run for many minutes. ``--monotone N`` adds a
+second hgbt fit with monotone constraints on the first N numeric columns
+(alternating +1 / -1) and reports its fit time and log-loss next to the
+unconstrained ones.
 
 ``--mode forest`` times HistForestClassifier (hrf; host binning, bootstrap
 draws and transfers included) against sklearn RandomForestClassifier on
@@ -103,6 +107,9 @@ def main(argv=None) -> None:
     ap.add_argument("--repeats", type=int, default=2,
                     help="hgbt fits; the first also pays one-time GPU start-up")
     ap.add_argument("--skip-exact-gbt", action="store_true")
+    ap.add_argument("--monotone", type=int, default=0, metavar="N",
+                    help="gbt mode: also fit hgbt with the first N numeric "
+                         "columns constrained, signs alternating from +1")
     a = ap.parse_args(argv)
 
     from sklearn.model_selection import train_test_split
@@ -142,6 +149,16 @@ def main(argv=None) -> None:
 
     run(f"hgbt[{a.device}]",
         lambda: HistGBTClassifier(**common, device=a.device), repeats=a.repeats)
+    if a.monotone:
+        from creditcore.schema import NUMERIC_FEATURES
+
+        n_num = len(NUMERIC_FEATURES)  # the numeric block is last
+        if not 1 <= a.monotone <= n_num:
+            ap.error(f"--monotone takes 1..{n_num}")
+        cst = {j - n_num: 1 - 2 * (j % 2) for j in range(a.monotone)}
+        run(f"hgbt_mono{a.monotone}[{a.device}]",
+            lambda: HistGBTClassifier(**common, device=a.device, monotone_cst=cst),
+            repeats=a.repeats)
     try:
         from sklearn.ensemble import HistGradientBoostingClassifier
     except ImportError:
@@ -161,6 +178,11 @@ def main(argv=None) -> None:
     print(json.dumps({
         "event": "summary", **shape,
         **{f"{k}_fit_s": v["fit_s"] for k, v in results.items()},
+        **{f"{k}_log_loss": v["log_loss"] for k, v in results.items()
+           if k.startswith("hgbt")},
+        **({"mono_over_plain_fit": round(
+            results[f"hgbt_mono{a.monotone}[{a.device}]"]["fit_s"] / ours, 3)}
+           if a.monotone else {}),
         **{f"speedup_vs_{k}": round(v["fit_s"] / ours, 2)
            for k, v in results.items() if not k.startswith("hgbt")},
     }), flush=True)

@@ -16,6 +16,22 @@ import json
 import sys
 
 
+def _monotone_arg(text: str) -> dict:
+    """``name=sign[,name=sign...]`` with sign in {-1, 0, +1} over the numeric
+    features, e.g. ``credit_limit=-1,payment_amount_1=-1``."""
+    from .schema import NUMERIC_FEATURES
+
+    out = {}
+    for item in text.split(","):
+        name, eq, sign = item.strip().partition("=")
+        if not eq or sign.strip() not in ("-1", "0", "1", "+1"):
+            raise argparse.ArgumentTypeError(f"expected name=-1|0|+1, got {item!r}")
+        if name.strip() not in NUMERIC_FEATURES:
+            raise argparse.ArgumentTypeError(f"{name.strip()!r} is not a numeric feature")
+        out[name.strip()] = int(sign)
+    return out
+
+
 def _cmd_train(argv):
     p = argparse.ArgumentParser(prog="creditcore train")
     p.add_argument("--model-dir", default="./model")
@@ -38,11 +54,18 @@ def _cmd_train(argv):
                    help="where --algorithm hgbt / hrf train: auto = the GPU "
                         "when one is visible (the other families train with "
                         "sklearn on the host)")
+    p.add_argument("--monotone", type=_monotone_arg, default=None,
+                   metavar="NAME=SIGN[,...]",
+                   help="monotone constraints for --algorithm hgbt over numeric "
+                        "features: +1 = the score never falls as the feature "
+                        "rises, -1 = never rises (credit_limit=-1,age=+1)")
     p.add_argument("--data", default=None,
                    help="CSV with the UCI schema (the reference's curated "
                         "table, 00-create-external-table.ipynb); synthetic "
                         "data is generated when omitted")
     a = p.parse_args(argv)
+    if a.monotone and a.algorithm != "hgbt":
+        p.error("--monotone needs --algorithm hgbt")
     from .train import train_and_register
 
     df = None
@@ -62,6 +85,7 @@ def _cmd_train(argv):
         algorithm=a.algorithm,
         min_roc_auc=a.min_roc_auc,
         train_device=a.train_device,
+        monotone=a.monotone,
     )
     print(uri)
 

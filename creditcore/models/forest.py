@@ -27,8 +27,32 @@ from sklearn.preprocessing import OneHotEncoder
 from ..schema import CATEGORICAL_FEATURES, MISSING_CATEGORY, NUMERIC_FEATURES
 
 
+def monotone_columns(monotone: dict) -> dict:
+    """{numeric feature name: sign} -> {encoded column index: sign} for
+    ``HistGBTClassifier(monotone_cst=...)``. The numeric block is last in the
+    ColumnTransformer, so name j of NUMERIC_FEATURES is column
+    j - len(NUMERIC_FEATURES) whatever the one-hot width turns out to be.
+    One-hot columns carry no order: a categorical name is an error."""
+    out = {}
+    for name, sign in dict(monotone).items():
+        if name in CATEGORICAL_FEATURES:
+            raise ValueError(
+                f"monotone constraint on categorical feature {name!r}: "
+                "one-hot columns are not ordered"
+            )
+        if name not in NUMERIC_FEATURES:
+            raise ValueError(f"monotone constraint on unknown feature {name!r}")
+        if sign not in (-1, 0, 1):
+            raise ValueError(f"monotone constraint for {name!r} must be -1, 0 or 1")
+        out[NUMERIC_FEATURES.index(name) - len(NUMERIC_FEATURES)] = int(sign)
+    return out
+
+
 def make_classifier_pipeline(params: dict, algorithm: str = "rf") -> Pipeline:
     """Build the classifier pipeline (reference 01-train cell-6).
+
+    ``params["monotone"]`` ({numeric feature name: -1 | 0 | +1}, "hgbt" only)
+    sets monotone constraints; see ``monotone_columns``.
 
     ``params`` are estimator kwargs (n_estimators / max_depth / random_state
     ...). ``algorithm``: "rf" (the reference's RandomForest), "gbt"
@@ -44,6 +68,10 @@ def make_classifier_pipeline(params: dict, algorithm: str = "rf") -> Pipeline:
     (ExtraTreesClassifier — identical tree structure and leaf-fraction-mean
     semantics to RF, so it rides the RF pack/score path unchanged).
     """
+    if params.get("monotone") and algorithm != "hgbt":
+        raise ValueError("monotone constraints need algorithm 'hgbt'")
+    if algorithm != "hgbt" and "monotone" in params:
+        params = {k: v for k, v in params.items() if k != "monotone"}
     if algorithm == "gbt":
         from sklearn.ensemble import GradientBoostingClassifier
 
@@ -59,6 +87,9 @@ def make_classifier_pipeline(params: dict, algorithm: str = "rf") -> Pipeline:
         params.setdefault("n_estimators", 200)
         if "max_depth" in params:  # the search space draws up to 24
             params["max_depth"] = min(int(params["max_depth"]), MAX_DEPTH)
+        monotone = params.pop("monotone", None)
+        if monotone:
+            params["monotone_cst"] = monotone_columns(monotone)
         estimator = HistGBTClassifier(**params)
     elif algorithm == "hrf":
         from .hrf import MAX_DEPTH, HistForestClassifier

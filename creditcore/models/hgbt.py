@@ -30,11 +30,34 @@ identical integer inputs:
 - leaf = -G/(H+l2) * learning_rate in f64, rounded to f32; it is computed on
   the host from the integer sums for both devices.
 
+Monotone constraints (``monotone_cst``: a sign in {-1, 0, +1} per encoded
+column) use the bounds propagation of XGBoost-hist, LightGBM "basic" and
+sklearn. Every open node carries f64 leaf-weight bounds [lo, hi], the root
+[-inf, +inf]. With g = G 2^-20 and d = H 2^-20 + l2,
+
+- a side takes w = min(max(-g/d, lo), hi) and scores s = -((2g)w + (dw)w);
+  gain = (s_L + s_R) - s_P with left, right and parent all clamped to the
+  node's bounds (one fixed operation order, no FMA contraction);
+- a split also needs d_L > 0, d_R > 0 and, on a +1 column, w_L <= w_R
+  (w_L >= w_R on a -1 column); ties break as above;
+- with mid = (w_L + w_R)/2 the children of a +1 split get [lo, mid] (left)
+  and [mid, hi] (right), of a -1 split [mid, hi] and [lo, mid]; a split on an
+  unconstrained column hands [lo, hi] to both. The bounds are computed on the
+  host from the split record's integer sums for both devices;
+- leaf = clamp(-g/d, lo, hi) * learning_rate in f64, rounded to f32. Rounding
+  and a positive rate keep the order, so every leaf under the lower child is
+  <= every leaf under the upper one exactly and the f64 sum over the trees is
+  monotone in the column.
+
+The search runs in hgbt_split_mono_kernel / cpu_ref.hgbt_split_mono_cpu.
+Without a non-zero sign the plain kernel and formula above run, so
+unconstrained models do not change. ``verify_monotone`` checks a fitted model.
+
 Limits: binary targets, ``max_depth <= 12``, ``max_bins <= 256``, no row or
-column subsampling, no monotone constraints, no native categorical splits
-(one-hot columns are ordinary 2-bin features), no missing-value direction
-(the pipeline imputes first). ``random_state`` is accepted for pipeline
-compatibility; training is deterministic without it.
+column subsampling, no native categorical splits (one-hot columns are
+ordinary 2-bin features, which a sign may not order usefully), no
+missing-value direction (the pipeline imputes first). ``random_state`` is
+accepted for pipeline compatibility; training is deterministic without it.
 
 The fitted state is plain numpy (sklearn-``tree_``-like flat arrays for all
 trees plus ``tree_offsets_``), so the estimator pickles without tensors and
@@ -125,6 +148,9 @@ class _CpuBackend:
     def split(self, hist, lam, min_leaf) -> np.ndarray:
         return self._ref.hgbt_split_cpu(hist, self.bin_off, lam, min_leaf)
 
+    def split_mono(self, hist, lam, min_leaf, mono, bounds) -> np.ndarray:
+        return self._ref.hgbt_split_mono_cpu(hist, self.bin_off, lam, min_leaf, mono, bounds)
+
     def route(self, node, table):
         return self._ref.hgbt_route_cpu(self.bins, table, node)
 
@@ -170,6 +196,7 @@ class _GpuBackend:
         self.rows_per_block = int(ext.HGBT_MAX_ROWS_PER_BLOCK)
         self.lds_bytes = LDS_BUDGET_BYTES
         self._groups: dict = {}
+        self._mono = None
 
     def new_nodes(self):
         return self._torch.zeros(self.n_rows, dtype=self._torch.int32, device=self.device)
@@ -198,6 +225,14 @@ class _GpuBackend:
         # the only per-level traffic back to the host: <= 2^depth records
         return self._ext.hgbt_split(hist, self.bin_off, lam, min_leaf).cpu().numpy()
 
+    def split_mono(self, hist, lam, min_leaf, mono, bounds) -> np.ndarray:
+        if self._mono is None or self._mono[0] is not mono:  # one upload per fit
+            self._mono = (mono, self._torch.from_numpy(mono).to(self.device))
+        return self._ext.hgbt_split_mono(
+            hist, self.bin_off, lam, min_leaf, self._mono[1],
+            self._torch.from_numpy(bounds).to(self.device),
+        ).cpu().numpy()
+
     def route(self, node, table):
         self._ext.hgbt_route(self.bins, self._torch.from_numpy(table).to(self.device), node)
         return node
@@ -213,6 +248,33 @@ def _leaf_values(g_sum: np.ndarray, h_sum: np.ndarray, lam: float, lr: float) ->
     return (v * lr).astype(np.float32)
 
 
+def _bounded_weights(g_sum, h_sum, lam: float, lo, hi) -> np.ndarray:
+    """clamp(-G/(H+l2), lo, hi) in f64 from the integer sums: the weight the
+    constrained split search gives a side (0 before the clamp when the
+    denominator is not positive, like ``_leaf_values``)."""
+    from ..ops.cpu_ref import hgbt_mono_weight
+
+    sc = 1.0 / float(1 << SHIFT)
+    g = g_sum.astype(np.float64) * sc
+    den = h_sum.astype(np.float64) * sc + lam
+    ok = den > 0.0
+    w = hgbt_mono_weight(np.where(ok, g, 0.0), np.where(ok, den, 1.0), lo, hi)
+    return np.asarray(w, dtype=np.float64)
+
+
+def _child_bounds(sign, w_l, w_r, lo, hi) -> np.ndarray:
+    """f64[n, 2, 2] bounds of the (left, right) children of n splits: a signed
+    split cuts the parent's [lo, hi] at mid = (w_L + w_R)/2, an unsigned one
+    hands it down."""
+    mid = (w_l + w_r) / 2.0
+    out = np.empty((len(mid), 2, 2), dtype=np.float64)
+    out[:, 0, 0] = np.where(sign < 0, mid, lo)
+    out[:, 0, 1] = np.where(sign > 0, mid, hi)
+    out[:, 1, 0] = np.where(sign > 0, mid, lo)
+    out[:, 1, 1] = np.where(sign < 0, mid, hi)
+    return out
+
+
 def grow_tree(
     backend,
     gq,
@@ -223,8 +285,13 @@ def grow_tree(
     lam: float,
     min_leaf: int,
     lr: float,
+    mono: np.ndarray | None = None,
 ):
     """Grow one tree level by level on ``backend`` from the int32 gradients.
+
+    ``mono`` (i32 per column, at least one non-zero sign) switches to the
+    constrained split search and carries a [lo, hi] weight-bounds row for
+    every open slot alongside ``active``; ``None`` is the plain trainer.
 
     Returns (tree, node): ``tree`` holds sklearn-style flat arrays
     (children_left/right, feature, threshold f32, value f32, cover i64) in
@@ -240,15 +307,24 @@ def grow_tree(
     n_used = 1
     node = backend.new_nodes()
     active = np.zeros(1, dtype=np.int64)  # tree node id of every open slot
+    bounds = np.asarray([[-np.inf, np.inf]])  # [lo, hi] of every open slot (mono)
     for depth in range(max_depth):
         k = len(active)
-        rec = backend.split(backend.hist(node, gq, hq, k), lam, min_leaf)
+        hist = backend.hist(node, gq, hq, k)
+        if mono is None:
+            rec = backend.split(hist, lam, min_leaf)
+        else:
+            rec = backend.split_mono(hist, lam, min_leaf, mono, bounds)
         feat, bin_ = rec[:, 1], rec[:, 2]
         g_l, h_l, c_l = rec[:, 3], rec[:, 4], rec[:, 5]
         g_t, h_t, c_t = rec[:, 6], rec[:, 7], rec[:, 8]
         if depth == 0:  # children get their sums from the parent's record
             cover[0] = c_t[0]
-            value[0] = _leaf_values(g_t, h_t, lam, lr)[0]
+            if mono is None:
+                value[0] = _leaf_values(g_t, h_t, lam, lr)[0]
+            else:
+                w = _bounded_weights(g_t, h_t, lam, bounds[:, 0], bounds[:, 1])
+                value[0] = (w * lr).astype(np.float32)[0]
         split = feat >= 0
         ns = int(split.sum())
         table = np.zeros((k, 4), dtype=np.int32)
@@ -268,7 +344,15 @@ def grow_tree(
             c_h = np.stack([h_l[split], (h_t - h_l)[split]], axis=1).ravel()
             c_c = np.stack([c_l[split], (c_t - c_l)[split]], axis=1).ravel()
             cover[child] = c_c
-            value[child] = _leaf_values(c_g, c_h, lam, lr)
+            if mono is None:
+                value[child] = _leaf_values(c_g, c_h, lam, lr)
+            else:
+                lo, hi = bounds[split, 0], bounds[split, 1]
+                w_l = _bounded_weights(c_g[0::2], c_h[0::2], lam, lo, hi)
+                w_r = _bounded_weights(c_g[1::2], c_h[1::2], lam, lo, hi)
+                c_b = _child_bounds(mono[feat[split]], w_l, w_r, lo, hi).reshape(-1, 2)
+                w = _bounded_weights(c_g, c_h, lam, c_b[:, 0], c_b[:, 1])
+                value[child] = (w * lr).astype(np.float32)
             # a child stays open while it may still split
             is_open = (c_c >= 2 * min_leaf) if depth + 1 < max_depth else np.zeros(
                 2 * ns, dtype=bool
@@ -279,6 +363,8 @@ def grow_tree(
             table[split, 2] = code[0::2]
             table[split, 3] = code[1::2]
             active = child[is_open]
+            if mono is not None:
+                bounds = np.ascontiguousarray(c_b[is_open])
         else:
             active = np.zeros(0, dtype=np.int64)
         node = backend.route(node, table)
@@ -315,6 +401,7 @@ class HistGBTClassifier(ClassifierMixin, BaseEstimator):
         min_samples_leaf=20,
         random_state=None,
         device="auto",
+        monotone_cst=None,
     ):
         self.n_estimators = n_estimators
         self.max_depth = max_depth
@@ -324,6 +411,7 @@ class HistGBTClassifier(ClassifierMixin, BaseEstimator):
         self.min_samples_leaf = min_samples_leaf
         self.random_state = random_state
         self.device = device
+        self.monotone_cst = monotone_cst
 
     # -- training ----------------------------------------------------------
     def _check_params(self):
@@ -339,6 +427,34 @@ class HistGBTClassifier(ClassifierMixin, BaseEstimator):
             raise ValueError("l2 must be >= 0")
         if self.device not in ("auto", "cpu", "cuda"):
             raise ValueError("device must be 'auto', 'cpu' or 'cuda'")
+
+    def _resolve_monotone(self, n_feat: int) -> np.ndarray:
+        """``monotone_cst`` as an i32 sign per encoded column: a sequence of
+        length n_feat, or {column index: sign} with negative indices counting
+        from the end (the pipeline's one-hot width is unknown before fit)."""
+        cst = self.monotone_cst
+        out = np.zeros(n_feat, dtype=np.int32)
+        if cst is None:
+            return out
+        if isinstance(cst, dict):
+            items = list(cst.items())
+        else:
+            if len(cst) != n_feat:
+                raise ValueError(
+                    f"monotone_cst has {len(cst)} entries for {n_feat} features"
+                )
+            items = list(enumerate(cst))
+        for idx, sign in items:
+            if isinstance(idx, (bool, np.bool_)) or int(idx) != idx:
+                raise ValueError(f"monotone_cst column index {idx!r} is not an integer")
+            if not -n_feat <= int(idx) < n_feat:
+                raise ValueError(
+                    f"monotone_cst column index {idx} out of range for {n_feat} features"
+                )
+            if sign not in (-1, 0, 1):
+                raise ValueError(f"monotone_cst values must be -1, 0 or 1, got {sign!r}")
+            out[int(idx)] = int(sign)
+        return out
 
     def _resolve_device(self) -> str:
         if self.device == "cpu":
@@ -369,6 +485,7 @@ class HistGBTClassifier(ClassifierMixin, BaseEstimator):
         p1 = float(np.clip(y01.mean(), 1e-12, 1.0 - 1e-12))
         self.init_raw_ = float(np.log(p1 / (1.0 - p1)))
         self.n_features_in_ = x.shape[1]
+        self.monotone_cst_ = self._resolve_monotone(x.shape[1])
 
         bins, bin_off, bin_thr = bin_features(x, int(self.max_bins))
         self.bin_offsets_ = bin_off
@@ -391,6 +508,9 @@ class HistGBTClassifier(ClassifierMixin, BaseEstimator):
             backend, gq, hq, bin_off, bin_thr,
             int(self.max_depth), float(self.l2), int(self.min_samples_leaf),
             float(self.learning_rate),
+            # the plain path stays as it is without a non-zero sign: the
+            # bounded score rounds differently from g^2/d even when idle
+            mono=self.monotone_cst_ if self.monotone_cst_.any() else None,
         )
 
     def _boost_cpu(self, bins, bin_off, bin_thr, y01):
@@ -482,3 +602,36 @@ class HistGBTClassifier(ClassifierMixin, BaseEstimator):
 
     def predict(self, X) -> np.ndarray:
         return self.classes_[(self.decision_function(X) > 0.0).astype(np.int64)]
+
+
+def verify_monotone(estimator, monotone_cst=None) -> bool:
+    """Structural check of a fitted model against its constraints.
+
+    True when, at every split on a constrained column, the largest leaf value
+    under the lower child does not exceed the smallest under the upper one
+    (lower = left for +1, right for -1). That makes every tree, and so their
+    f64 sum, monotone in the column. ``estimator`` is a fitted
+    ``HistGBTClassifier`` or a pipeline ending in one; ``monotone_cst``
+    (a sign per encoded column) overrides the fitted ``monotone_cst_``, e.g.
+    to ask whether an unconstrained model happens to comply."""
+    clf = estimator
+    if hasattr(estimator, "named_steps"):
+        clf = estimator.named_steps["classifier"]
+    sign = clf.monotone_cst_ if monotone_cst is None else np.asarray(monotone_cst)
+    if len(sign) != clf.n_features_in_:
+        raise ValueError("monotone_cst must have one sign per encoded column")
+    for i in range(clf.n_trees_):
+        t = clf.tree_arrays(i)
+        left, right, feat = t["children_left"], t["children_right"], t["feature"]
+        lo = t["value"].copy()  # smallest / largest leaf of every subtree
+        hi = t["value"].copy()
+        # children follow their parent in creation order: one reverse sweep
+        for n in range(len(left) - 1, -1, -1):
+            a, b = left[n], right[n]
+            if a < 0:
+                continue
+            s = sign[feat[n]]
+            if (s > 0 and hi[a] > lo[b]) or (s < 0 and hi[b] > lo[a]):
+                return False
+            lo[n], hi[n] = min(lo[a], lo[b]), max(hi[a], hi[b])
+    return True

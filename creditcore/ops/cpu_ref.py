@@ -640,6 +640,83 @@ def hgbt_split_cpu(
     return out
 
 
+def hgbt_mono_weight(g: np.ndarray, d: np.ndarray, lo, hi) -> np.ndarray:
+    """Newton weight -g/d clamped to [lo, hi]. The clamp is two selects, not
+    np.clip, so that it picks the operand the kernel's compares pick."""
+    w = -g / d
+    w = np.where(w < lo, lo, w)
+    return np.where(w > hi, hi, w)
+
+
+def hgbt_split_mono_cpu(
+    hist: np.ndarray,
+    bin_off: np.ndarray,
+    lam: float,
+    min_leaf: int,
+    mono: np.ndarray,
+    bounds: np.ndarray,
+) -> np.ndarray:
+    """Best split per open node under monotone constraints, i64[n_nodes,
+    HGBT_REC] (golden reference of hgbt_split_mono).
+
+    ``mono`` i32[F] is the sign of every feature (-1, 0, +1; only the sign is
+    read), ``bounds`` f64[n_nodes, 2] the leaf-weight interval {lo, hi} of
+    every open node. With g = G 2^-SHIFT and d = H 2^-SHIFT + lam, a side
+    takes w = min(max(-g/d, lo), hi) and scores s = -((2g)w + (dw)w); left,
+    right and parent are all clamped to the node's interval and
+    gain = (s_L + s_R) - s_P. A candidate is valid when both sides keep
+    ``min_leaf`` rows, d_L > 0 and d_R > 0, gain > 0, and w_L <= w_R on a
+    +1 feature (w_L >= w_R on a -1 feature). Ties and the no-split record are
+    hgbt_split_cpu's."""
+    n_nodes, _, total = hist.shape
+    bin_off = np.asarray(bin_off, dtype=np.int64)
+    out = np.zeros((n_nodes, HGBT_REC), dtype=np.int64)
+    if n_nodes == 0:
+        return out
+    feat_of_bin = np.repeat(np.arange(len(bin_off) - 1), np.diff(bin_off))
+    start = bin_off[:-1][feat_of_bin]
+    cs = np.cumsum(hist, axis=2)
+    before = np.where(start > 0, cs[:, :, np.maximum(start - 1, 0)], 0)
+    pre = cs - before
+    f0_last = int(bin_off[1]) - 1
+    tot = pre[:, :, f0_last]
+    GL, HL, CL = pre[:, 0], pre[:, 1], pre[:, 2]
+    G, H, C = tot[:, 0:1], tot[:, 1:2], tot[:, 2:3]
+    sign = np.sign(np.asarray(mono, dtype=np.int64))[feat_of_bin][None, :]
+    bounds = np.asarray(bounds, dtype=np.float64).reshape(n_nodes, 2)
+    lo, hi = bounds[:, 0:1], bounds[:, 1:2]
+    sc = 1.0 / float(1 << HGBT_SHIFT)
+
+    def side(g_int, h_int):
+        g = g_int.astype(np.float64) * sc
+        d = h_int.astype(np.float64) * sc + lam
+        w = hgbt_mono_weight(g, d, lo, hi)
+        return d, w, -(((2.0 * g) * w) + ((d * w) * w))
+
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        d_l, w_l, s_l = side(GL, HL)
+        d_r, w_r, s_r = side(G - GL, H - HL)
+        _, _, s_p = side(G, H)
+        gain = (s_l + s_r) - s_p
+        order = (sign == 0) | ((sign > 0) & (w_l <= w_r)) | ((sign < 0) & (w_l >= w_r))
+        valid = (
+            (CL >= min_leaf) & (C - CL >= min_leaf)
+            & (d_l > 0.0) & (d_r > 0.0) & (gain > 0.0) & order
+        )
+    gain = np.where(valid, gain, -np.inf)
+    best = np.argmax(gain, axis=1)
+    k = np.arange(n_nodes)
+    ok = valid[k, best]
+    out[:, 0] = np.where(ok, gain[k, best], 0.0).view(np.int64)
+    out[:, 1] = np.where(ok, feat_of_bin[best], -1)
+    out[:, 2] = np.where(ok, best - start[best], 0)
+    out[:, 3] = np.where(ok, GL[k, best], 0)
+    out[:, 4] = np.where(ok, HL[k, best], 0)
+    out[:, 5] = np.where(ok, CL[k, best], 0)
+    out[:, 6:9] = tot
+    return out
+
+
 def hgbt_route_cpu(bins: np.ndarray, table: np.ndarray, node: np.ndarray) -> np.ndarray:
     """New per-row node ids. ``table[k] = {feat, bin, left, right}`` for open
     node k: rows with bins[feat] <= bin take ``left``, the others ``right``;

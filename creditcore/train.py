@@ -62,10 +62,15 @@ class EvalRun:
     pipeline: object = field(repr=False, default=None)
 
 
-def _family_params(params: dict, algorithm: str, train_device: str) -> dict:
+def _family_params(
+    params: dict, algorithm: str, train_device: str, monotone: dict | None = None
+) -> dict:
     """Map a draw from the reference search space onto the estimator family:
     hgbt and hrf have no split criterion choice (hrf is Gini only), cap
-    max_depth and take a training device."""
+    max_depth and take a training device; hgbt alone takes ``monotone``
+    ({numeric feature name: sign}, models/forest.py)."""
+    if monotone and algorithm != "hgbt":
+        raise ValueError("monotone constraints need algorithm 'hgbt'")
     if algorithm not in ("hgbt", "hrf"):
         return params
     from .models.hgbt import MAX_DEPTH  # models/hrf.py shares the limit
@@ -74,6 +79,8 @@ def _family_params(params: dict, algorithm: str, train_device: str) -> dict:
     if "max_depth" in out:
         out["max_depth"] = min(int(out["max_depth"]), MAX_DEPTH)
     out["device"] = train_device
+    if monotone:
+        out["monotone"] = {str(k): int(v) for k, v in monotone.items()}
     return out
 
 
@@ -83,6 +90,7 @@ def _evaluate(
     seed: int = 2024,
     algorithm: str = "rf",
     train_device: str = "auto",
+    monotone: dict | None = None,
 ) -> EvalRun:
     """One hyperparameter evaluation (reference cell-7, minus the dead
     double-fits)."""
@@ -92,7 +100,7 @@ def _evaluate(
     x_train, y_train = df_train[FEATURES], df_train[TARGET]
     x_test, y_test = df_test[FEATURES], df_test[TARGET]
 
-    fit_params = _family_params(params, algorithm, train_device)
+    fit_params = _family_params(params, algorithm, train_device, monotone)
     estimator = make_classifier_pipeline({**fit_params, "random_state": seed}, algorithm)
     estimator.fit(x_train, y_train.values.ravel())
     y_pred = estimator.predict(x_test)
@@ -117,6 +125,7 @@ def train_model(
     n_rows: int = 20_000,
     algorithm: str = "rf",
     train_device: str = "auto",
+    monotone: dict | None = None,
 ) -> EvalRun:
     """Hyperparameter search with a real TPE sampler (reference cell-8:
     hyperopt fmin(tpe.suggest, max_evals=10); hyperopt itself is
@@ -132,7 +141,8 @@ def train_model(
     for i in range(max_evals):
         params = sampler.suggest()
         run = _evaluate(
-            params, df, seed=seed, algorithm=algorithm, train_device=train_device
+            params, df, seed=seed, algorithm=algorithm, train_device=train_device,
+            monotone=monotone,
         )
         # hyperopt minimizes; the notebook returns -roc_auc as the loss
         sampler.observe(params, -run.metrics["validation_roc_auc_score"])
@@ -182,15 +192,22 @@ def train_and_register(
     algorithm: str = "rf",
     min_roc_auc: float | None = None,
     train_device: str = "auto",
+    monotone: dict | None = None,
+    runs_dir: str | None = None,
 ) -> str:
     """The full train -> package -> register job (the reference's 2-task
     Databricks DAG, train_register_model.yml:10-39). Returns the model URI
-    (or the model dir when register=False)."""
+    (or the model dir when register=False). ``monotone`` ({numeric feature
+    name: -1 | +1}, hgbt only) constrains every evaluated model; the best one
+    is checked with ``verify_monotone`` before it is saved. ``runs_dir`` keeps
+    one ``run.json`` per evaluation (``train_model``)."""
+    if monotone and algorithm != "hgbt":
+        raise ValueError("monotone constraints need algorithm 'hgbt'")
     if df is None:
         df = make_uci_shaped_frame(n_rows=n_rows, seed=seed)
     best = train_model(
         df=df, max_evals=max_evals, seed=seed, algorithm=algorithm,
-        train_device=train_device,
+        train_device=train_device, monotone=monotone, runs_dir=runs_dir,
     )
     if min_roc_auc is not None:
         auc = best.metrics["validation_roc_auc_score"]
@@ -200,6 +217,13 @@ def train_and_register(
             raise QualityGateError(
                 f"best validation_roc_auc_score {auc:.4f} < gate {min_roc_auc}"
             )
+    extra = {"best_params": best.params, "best_metrics": best.metrics}
+    if monotone:
+        from .models.hgbt import verify_monotone
+
+        if not verify_monotone(best.pipeline):
+            raise RuntimeError("the best model violates its monotone constraints")
+        extra["monotone"] = dict(best.params["monotone"])
     drift, outlier = fit_detectors(df)
     registry.save_pyfunc_model(
         model_dir,
@@ -208,7 +232,7 @@ def train_and_register(
         outlier,
         input_example=INPUT_SAMPLE,
         run_id=best.run_id,
-        extra_metadata={"best_params": best.params, "best_metrics": best.metrics},
+        extra_metadata=extra,
     )
     if not register:
         return model_dir

@@ -1658,6 +1658,122 @@ __global__ __launch_bounds__(HGBT_BLOCK) void hgbt_split_kernel(
   }
 }
 
+// Monotone-constrained split search (models/hgbt.py, "monotone constraints").
+// A side with sums (g, d = h + lam) and the node's weight bounds [lo, hi]
+// takes the clamped Newton weight w and scores -(2 g w + d w^2), which is
+// g^2/d when the clamp is idle. Operation order is hgbt_split_mono_cpu's and
+// contraction is off (see hgbt_gain). The clamp is written as compares so
+// that it selects the same operand as the reference's np.where.
+__device__ __forceinline__ double hgbt_mono_score(
+    double g, double d, double lo, double hi, double* w_out)
+{
+#pragma clang fp contract(off)
+  double w = -g / d;
+  w = w < lo ? lo : w;
+  w = w > hi ? hi : w;
+  *w_out = w;
+  const double a = (2.0 * g) * w;
+  const double b = (d * w) * w;
+  return -(a + b);
+}
+
+// hgbt_split_kernel's decomposition (one block per open node, 4 wavefronts
+// striding the features, 4 bins per lane, shuffle scan, xor-shuffle + LDS
+// reduction) with the bounds-propagation rule of XGBoost-hist / LightGBM
+// "basic": mono[f] in {-1, 0, +1} is feature f's sign, bounds[k] = {lo, hi}
+// the leaf-weight interval of open node k. Left, right and parent are clamped
+// to the node's interval; a candidate also needs d_L > 0, d_R > 0 and, on a
+// signed feature, w_L <= w_R (+1) or w_L >= w_R (-1).
+__global__ __launch_bounds__(HGBT_BLOCK) void hgbt_split_mono_kernel(
+    const long long* __restrict__ hist, const int* __restrict__ bin_off,
+    const int* __restrict__ mono, const double* __restrict__ bounds,
+    int n_feat, int total_bins, double lam, long long min_leaf,
+    long long* __restrict__ out)
+{
+#pragma clang fp contract(off)
+  __shared__ HgbtBest wave_best[HGBT_BLOCK / 64];
+  __shared__ long long wave_tot[HGBT_BLOCK / 64][3];
+  const int k = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long* hg = hist + (size_t)k * 3 * total_bins;
+  const long long* hh = hg + total_bins;
+  const long long* hc = hh + total_bins;
+  const double lo = bounds[2 * (size_t)k], hi = bounds[2 * (size_t)k + 1];
+  const double scale = 1.0 / (double)(1 << HGBT_SHIFT);
+
+  HgbtBest best;
+  best.gain = 0.0; best.feat = -1; best.bin = 0; best.GL = best.HL = best.CL = 0;
+  long long G = 0, H = 0, C = 0;
+  for (int f = wave; f < n_feat; f += HGBT_BLOCK / 64) {
+    const int fb = bin_off[f];
+    const int nb = bin_off[f + 1] - fb;
+    if (fb < 0 || nb <= 0 || nb > HGBT_MAX_BINS || fb + nb > total_bins) continue;
+    const int sign = mono[f];
+    long long pg[4], ph[4], pc[4];
+    long long sg = 0, sh = 0, sc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int b = lane * 4 + j;
+      if (b < nb) { sg += hg[fb + b]; sh += hh[fb + b]; sc += hc[fb + b]; }
+      pg[j] = sg; ph[j] = sh; pc[j] = sc;
+    }
+    // inclusive scan of the lane totals across the wavefront
+    long long ig = sg, ih = sh, ic = sc;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const long long tg = __shfl_up(ig, d), th = __shfl_up(ih, d), tc = __shfl_up(ic, d);
+      if (lane >= d) { ig += tg; ih += th; ic += tc; }
+    }
+    G = __shfl(ig, 63); H = __shfl(ih, 63); C = __shfl(ic, 63);
+    // parent weight and score: once per feature, from the node totals
+    double w_p;
+    const double s_p =
+        hgbt_mono_score((double)G * scale, (double)H * scale + lam, lo, hi, &w_p);
+    const long long og = ig - sg, oh = ih - sh, oc = ic - sc;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int b = lane * 4 + j;
+      if (b >= nb) continue;
+      const long long CL = oc + pc[j];
+      if (CL < min_leaf || C - CL < min_leaf) continue;
+      HgbtBest c;
+      c.GL = og + pg[j]; c.HL = oh + ph[j]; c.CL = CL;
+      c.feat = f; c.bin = b;
+      const double d_l = (double)c.HL * scale + lam;
+      const double d_r = (double)(H - c.HL) * scale + lam;
+      if (!(d_l > 0.0) || !(d_r > 0.0)) continue;
+      double w_l, w_r;
+      const double s_l = hgbt_mono_score((double)c.GL * scale, d_l, lo, hi, &w_l);
+      const double s_r = hgbt_mono_score((double)(G - c.GL) * scale, d_r, lo, hi, &w_r);
+      c.gain = (s_l + s_r) - s_p;
+      if (!(c.gain > 0.0)) continue;
+      if (sign > 0 && !(w_l <= w_r)) continue;
+      if (sign < 0 && !(w_l >= w_r)) continue;
+      if (hgbt_better(c, best)) best = c;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const HgbtBest o = hgbt_shfl_xor(best, m);
+    if (hgbt_better(o, best)) best = o;
+  }
+  if (lane == 0) {
+    wave_best[wave] = best;
+    wave_tot[wave][0] = G; wave_tot[wave][1] = H; wave_tot[wave][2] = C;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < HGBT_BLOCK / 64; ++w)
+      if (hgbt_better(wave_best[w], best)) best = wave_best[w];
+    // wave 0 always scans feature 0 (n_feat >= 1), so its totals are set
+    long long* o = out + (size_t)k * HGBT_REC;
+    o[0] = __double_as_longlong(best.feat < 0 ? 0.0 : best.gain);
+    o[1] = best.feat; o[2] = best.bin;
+    o[3] = best.GL; o[4] = best.HL; o[5] = best.CL;
+    o[6] = wave_tot[0][0]; o[7] = wave_tot[0][1]; o[8] = wave_tot[0][2];
+  }
+}
+
 // table[k] = {feat, bin, left, right} for open node k: rows with
 // bins[feat] <= bin take `left`, the others `right`; feat < 0 closes the node
 // and every row takes `left`. A target >= 0 is the child's slot in the next
@@ -1767,6 +1883,46 @@ torch::Tensor hgbt_split(torch::Tensor hist, torch::Tensor bin_off,
   hipLaunchKernelGGL(hgbt_split_kernel, dim3((unsigned)K), dim3(HGBT_BLOCK), 0, stream,
       reinterpret_cast<const long long*>(hist.data_ptr<int64_t>()),
       bin_off.data_ptr<int>(), (int)(bin_off.size(0) - 1), (int)hist.size(2), lam, (long long)min_leaf,
+      reinterpret_cast<long long*>(out.data_ptr<int64_t>()));
+  HIP_CHECK(hipGetLastError());
+  return out;
+}
+
+// Best split per open node under monotone constraints: mono i32[F] holds the
+// sign of every feature (only the sign is read), bounds f64[n_nodes, 2] the
+// {lo, hi} leaf-weight interval of every open node. Records as hgbt_split.
+torch::Tensor hgbt_split_mono(torch::Tensor hist, torch::Tensor bin_off,
+                              double lam, int64_t min_leaf,
+                              torch::Tensor mono, torch::Tensor bounds)
+{
+  TORCH_CHECK(hist.is_cuda() && hist.scalar_type() == torch::kInt64 &&
+              hist.dim() == 3 && hist.size(1) == 3 && hist.is_contiguous(),
+              "hist must be a contiguous i64[n_nodes, 3, total_bins] GPU tensor");
+  hgbt_check(bin_off, hist, torch::kInt32, "bin_off");
+  TORCH_CHECK(bin_off.dim() == 1 && bin_off.size(0) >= 2, "bin_off must be i32[F+1]");
+  TORCH_CHECK(min_leaf >= 1, "min_leaf must be >= 1");
+  const int64_t K = hist.size(0), F = bin_off.size(0) - 1;
+  hgbt_check(mono, hist, torch::kInt32, "mono");
+  TORCH_CHECK(mono.dim() == 1 && mono.size(0) == F, "mono must be i32[F]");
+  hgbt_check(bounds, hist, torch::kFloat64, "bounds");
+  TORCH_CHECK(bounds.dim() == 2 && bounds.size(0) == K && bounds.size(1) == 2,
+              "bounds must be f64[n_nodes, 2]");
+  c10::hip::HIPGuard guard((c10::DeviceIndex)hist.get_device());
+  auto out = torch::zeros({K, HGBT_REC},
+      torch::TensorOptions().dtype(torch::kInt64).device(hist.device()));
+  if (K == 0) return out;
+  {  // K pairs: one small copy, checked on the host
+    const auto host = bounds.cpu();
+    const double* b = host.data_ptr<double>();
+    for (int64_t k = 0; k < K; ++k)
+      TORCH_CHECK(b[2 * k] <= b[2 * k + 1],
+                  "bounds need lo <= hi and no NaN (node ", k, ")");
+  }
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(hgbt_split_mono_kernel, dim3((unsigned)K), dim3(HGBT_BLOCK), 0, stream,
+      reinterpret_cast<const long long*>(hist.data_ptr<int64_t>()),
+      bin_off.data_ptr<int>(), mono.data_ptr<int>(), bounds.data_ptr<double>(),
+      (int)F, (int)hist.size(2), lam, (long long)min_leaf,
       reinterpret_cast<long long*>(out.data_ptr<int64_t>()));
   HIP_CHECK(hipGetLastError());
   return out;
@@ -3887,6 +4043,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hgbt_split", &hgbt_split,
         "HistGBT best split per open node, i64[n_nodes,9] records (gfx950)",
         py::arg("hist"), py::arg("bin_off"), py::arg("lam"), py::arg("min_leaf"));
+  m.def("hgbt_split_mono", &hgbt_split_mono,
+        "HistGBT best split per open node under monotone constraints: feature "
+        "signs i32[F], per-node weight bounds f64[n_nodes,2] (gfx950)",
+        py::arg("hist"), py::arg("bin_off"), py::arg("lam"), py::arg("min_leaf"),
+        py::arg("mono"), py::arg("bounds"));
   m.def("hgbt_route", &hgbt_route,
         "HistGBT: move rows to their child node or leaf, in place (gfx950)",
         py::arg("bins"), py::arg("table"), py::arg("node"));
