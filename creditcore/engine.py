@@ -151,6 +151,19 @@ class ScoringEngine:
     # profiles/bench_results/ishap_micro.txt. A larger background override
     # lengthens even a one-row launch (its floor grows with R).
     ISHAP_MAX_PAIRS = 4096
+    # method="shap" with interactions=True: per-call row cap (a row of the
+    # result is a 23 x 23 matrix, 529 numbers) ...
+    INTERACTION_MAX_ROWS = 128
+    # ... and most rows of one forest_shap_interactions launch; a call above
+    # it runs as several launches over row slices. Sized like ISHAP_MAX_PAIRS:
+    # the largest multiple of the kernel's rows per block (16), up to the
+    # call cap, whose launch on the flagship forest is no longer than 1.25 x
+    # the method="shap" launch at SHAP_MAX_ROWS measured in the same run:
+    # forest_shap at 1024 rows 60.17 ms (bound 75.21 ms),
+    # forest_shap_interactions at 128 rows 51.99 ms on an MI355X,
+    # profiles/bench_results/shap_inter_micro.txt. Every row count up to the
+    # call cap is within the bound, so today no call is sliced.
+    INTERACTION_LAUNCH_ROWS = 128
 
     def __init__(
         self,
@@ -276,6 +289,7 @@ class ScoringEngine:
         nums: np.ndarray,
         method: str = "saabas",
         background=None,
+        interactions: bool = False,
     ) -> dict:
         """Per-row attributions for the classifier: prediction-path (Saabas)
         contributions by default, exact path-dependent TreeSHAP values with
@@ -286,7 +300,12 @@ class ScoringEngine:
         ``background_rows``; ``base_value`` is then the mean model output
         over the background rows; same row cap). ``background`` is an
         optional encoded ``(codes, nums)`` pair that replaces the packed
-        sample for that method.
+        sample for that method. ``interactions=True`` (``method="shap"``
+        only, capped at INTERACTION_MAX_ROWS) adds ``interactions``
+        f64[B, 23, 23]: exact SHAP interaction values, symmetric, each
+        off-diagonal entry half of the pair's interaction, the diagonal the
+        feature's SHAP value minus its off-diagonal row sum, so that
+        ``interactions.sum(2)`` is ``contributions``.
 
         Returns ``contributions`` f64[B, 23] in schema.FEATURES order,
         ``base_value``, ``output_space`` ("probability" for the averaging
@@ -299,12 +318,14 @@ class ScoringEngine:
             raise ValueError(
                 f"unknown explain method {method!r}; expected one of {EXPLAIN_METHODS}"
             )
+        if interactions and method != "shap":
+            raise ValueError("interactions=True applies to method='shap' only")
         if method == "interventional":
             return self._explain_ishap(codes, nums, background)
         if background is not None:
             raise ValueError("background= applies to method='interventional' only")
         if method == "shap":
-            return self._explain_shap(codes, nums)
+            return self._explain_shap(codes, nums, interactions)
         if p.cls_node_value is None:
             raise ExplainUnavailable(
                 "model was packed without per-node expected values; "
@@ -384,7 +405,9 @@ class ScoringEngine:
                 )
                 return out.cpu().numpy()  # D2H copy synchronizes the stream
 
-    def _explain_shap(self, codes: np.ndarray, nums: np.ndarray) -> dict:
+    def _explain_shap(
+        self, codes: np.ndarray, nums: np.ndarray, interactions: bool = False
+    ) -> dict:
         p = self.packed
         if p.cls_node_cover is None:
             raise ExplainUnavailable(
@@ -392,6 +415,11 @@ class ScoringEngine:
                 "the trained pipeline to enable SHAP attributions"
             )
         b = len(codes)
+        if interactions and b > self.INTERACTION_MAX_ROWS:
+            raise ExplainTooLarge(
+                f"explain with interactions is capped at "
+                f"{self.INTERACTION_MAX_ROWS} rows per call (got {b})"
+            )
         if b > self.SHAP_MAX_ROWS:
             raise ExplainTooLarge(
                 f"explain with method='shap' is capped at {self.SHAP_MAX_ROWS} "
@@ -409,14 +437,62 @@ class ScoringEngine:
                 contrib = cpu_ref.forest_shap_cpu(
                     p, codes, cpu_ref.impute_nums(p, nums), paths=paths
                 )
+            inter = self._shap_inter(paths, codes, nums) if interactions else None
         raw = base + contrib.sum(axis=1)
         log_odds = int(getattr(p, "cls_kind", 0)) == 1
-        return {
+        out = {
             "contributions": contrib,
             "base_value": base,
             "output_space": "log_odds" if log_odds else "probability",
             "predictions": 1.0 / (1.0 + np.exp(-raw)) if log_odds else raw,
         }
+        if inter is not None:
+            # the diagonal closes every row of the matrix onto the SHAP value
+            d = np.arange(N_CAT + N_NUM)
+            inter[:, d, d] = 0.0
+            inter[:, d, d] = contrib - inter.sum(axis=2)
+            out["interactions"] = inter
+        return out
+
+    def _shap_inter(self, paths, codes: np.ndarray, nums: np.ndarray) -> np.ndarray:
+        """Off-diagonal SHAP interaction values f64[B, 23, 23] (the diagonal
+        is the caller's), at most INTERACTION_LAUNCH_ROWS rows per launch;
+        the caller holds _explain_lock."""
+        p = self.packed
+        if self.device == "cuda":
+            import torch
+
+            ext = self._gpu["ext"]
+            dev = torch.device("cuda", self.device_index)
+            m = self._path_table_dev(paths)
+
+            def run(c: np.ndarray, x: np.ndarray) -> np.ndarray:
+                with torch.cuda.device(dev):
+                    out = ext.forest_shap_interactions(
+                        torch.from_numpy(c).to(dev),
+                        torch.from_numpy(x).to(dev),
+                        m["leaf_value"],
+                        m["leaf_off"],
+                        m["splits"],
+                        m["medians"],
+                        int(getattr(p, "cls_kind", 0)),
+                        int(p.cls_n_trees),
+                    )
+                    return out.cpu().numpy()  # D2H copy synchronizes the stream
+        else:
+            def run(c, x):
+                return cpu_ref.forest_shap_interactions_cpu(
+                    p, c, cpu_ref.impute_nums(p, x), paths=paths
+                )
+        step = max(1, int(self.INTERACTION_LAUNCH_ROWS))
+        parts = [
+            run(codes[s : s + step], nums[s : s + step])
+            for s in range(0, len(codes), step)
+        ]
+        n_src = N_CAT + N_NUM
+        if not parts:
+            return np.zeros((0, n_src, n_src), dtype=np.float64)
+        return np.concatenate(parts)
 
     def _path_table(self):
         """(path table, SHAP base value), built and bounds-checked once; the
@@ -572,10 +648,18 @@ class ScoringEngine:
             )
             return out.cpu().numpy()  # D2H copy synchronizes the stream
 
-    def explain_records(self, records, method: str = "saabas", background=None) -> dict:
+    def explain_records(
+        self,
+        records,
+        method: str = "saabas",
+        background=None,
+        interactions: bool = False,
+    ) -> dict:
         """explain_arrays on a request body (list of dicts / DataFrame)."""
         codes, nums = encode_batch(records, self.packed.vocabs)
-        return self.explain_arrays(codes, nums, method=method, background=background)
+        return self.explain_arrays(
+            codes, nums, method=method, background=background, interactions=interactions
+        )
 
     def encode_json_body(self, body: bytes) -> tuple:
         """Parse a raw /score JSON body into (codes, nums) with the native C

@@ -249,6 +249,128 @@ def forest_shap_cpu(
     return acc * scale
 
 
+def forest_shap_interactions_cpu(
+    packed: PackedModel,
+    codes: np.ndarray,
+    nums_imp: np.ndarray,
+    paths=None,
+    max_bytes: int = 64 << 20,
+) -> np.ndarray:
+    """Exact path-dependent SHAP interaction values, f64[B, 23, 23] in schema
+    feature order on both axes (one-hot features fold onto their categorical
+    column), in the convention of the ``shap`` package: the matrix is
+    symmetric, each off-diagonal entry holds half of the pair's Shapley
+    interaction index, and the diagonal is phi_i - sum_{j != i} Phi_ij with
+    phi = forest_shap_cpu, so that every row sums to the SHAP value of its
+    feature and the whole matrix plus the SHAP base value is the model output.
+
+    Per leaf with value v and distinct players p on its path (z_p, o_p as in
+    forest_shap_cpu), for i != j:
+
+        Phi_ij = v/2 (o_i - z_i)(o_j - z_j)
+                 * int_0^1 prod_{p != i,j} (z_p (1-t) + o_p t) dt
+
+    evaluated with the same 12-point Gauss-Legendre rule as
+    sum_q w_q L_q g_iq g_jq, L_q = prod_p f_pq, g_pq = (o_p - z_p) / f_pq.
+    f_pq = 0 only for an off player with z_p = 0; the leaf then contributes
+    nothing to the row (L_q = 0) and g is taken as 0, so exact zeros stay
+    exact. Same f32 compares as score_forest_cpu; everything else is f64.
+    Leaves are processed in chunks so that temporaries stay under
+    ``max_bytes``."""
+    from ..pack import (
+        SHAP_CODE_SHIFT,
+        SHAP_DIR_RIGHT,
+        SHAP_FIRST,
+        SHAP_PLAYER_SHIFT,
+        build_shap_paths,
+    )
+
+    if paths is None:
+        paths, _ = build_shap_paths(packed)
+    codes = np.asarray(codes)
+    n_rows = len(codes)
+    n_src = N_CAT + N_NUM
+    out = np.zeros((n_rows, n_src, n_src), dtype=np.float64)
+    off = paths.leaf_off.astype(np.int64)
+    if n_rows == 0 or int(off[-1]) == 0:
+        return out
+    phi = forest_shap_cpu(packed, codes, nums_imp, paths=paths, max_bytes=max_bytes)
+
+    sp = paths.splits
+    thr = sp[:, 1].view(np.float32)
+    frac = sp[:, 2].view(np.float32).astype(np.float64)
+    flags = sp[:, 3].view(np.uint32).astype(np.int64)
+    right = (flags & SHAP_DIR_RIGHT) != 0
+    first = (flags & SHAP_FIRST) != 0
+    player = (flags >> SHAP_PLAYER_SHIFT) & 0xFF
+    code = (flags >> SHAP_CODE_SHIFT) - 1
+
+    gstart = np.flatnonzero(first)
+    n_leaves = paths.n_leaves
+    rec_leaf = np.repeat(np.arange(n_leaves), np.diff(off))
+    leaf_goff = np.zeros(len(off), dtype=np.int64)  # first group of each leaf
+    np.cumsum(np.bincount(rec_leaf[gstart], minlength=n_leaves), out=leaf_goff[1:])
+    z_all = np.multiply.reduceat(frac, gstart)
+    g_player = player[gstart]
+    leaf_v = paths.leaf_value.astype(np.float64)
+
+    t = SHAP_T[None, None, :]
+    # upper triangle, keyed lo * n_src + hi, transposed so that np.add.at
+    # adds whole [B] rows
+    acc = np.zeros((n_src * n_src, n_rows), dtype=np.float64)
+    # per group: f, g and the gathers of a pair step — ~6 x [B, G, NQ] f64
+    g_max = max(1, max_bytes // (6 * 8 * SHAP_NQ * n_rows))
+    a = 0
+    while a < n_leaves:
+        b = int(np.searchsorted(leaf_goff, leaf_goff[a] + g_max, side="right")) - 1
+        b = min(max(b, a + 1), n_leaves)
+        g0, g1 = int(leaf_goff[a]), int(leaf_goff[b])
+        r0, r1 = int(off[a]), int(off[b])
+        n_g = leaf_goff[a + 1 : b + 1] - leaf_goff[a:b]
+        if g1 == g0 or int(n_g.max()) < 2:
+            a = b
+            continue
+        cat = code[r0:r1] >= 0
+        pl = player[r0:r1]
+        x = np.empty((n_rows, r1 - r0), dtype=np.float32)
+        x[:, cat] = codes[:, pl[cat]] == code[r0:r1][cat][None, :]
+        x[:, ~cat] = nums_imp[:, pl[~cat] - N_CAT]
+        follows = ~(x <= thr[None, r0:r1]) == right[None, r0:r1]
+        o = np.logical_and.reduceat(follows, gstart[g0:g1] - r0, axis=1)
+        o = o.astype(np.float64)[:, :, None]
+        z = z_all[g0:g1][None, :, None]
+        f = z * (1.0 - t) + o * t  # [B, G, NQ]
+        ne = n_g > 0
+        lg = (leaf_goff[a:b] - g0)[ne]
+        # w_q v/2 L_q per non-empty leaf
+        lw = np.multiply.reduceat(f, lg, axis=1) * SHAP_W[None, None, :]
+        lw *= (0.5 * leaf_v[a:b][ne])[None, :, None]
+        dead = f == 0.0
+        np.copyto(f, 1.0, where=dead)
+        g = (o - z) / f
+        np.copyto(g, 0.0, where=dead)
+        n_ne = n_g[ne]
+        for j in range(1, int(n_ne.max())):
+            sel = np.flatnonzero(n_ne > j)
+            gj = lg[sel] + j
+            lwg = lw[:, sel] * g[:, gj]
+            for i in range(j):
+                gi = lg[sel] + i
+                val = (lwg * g[:, gi]).sum(axis=2)  # [B, leaves with > j groups]
+                pi, pj = g_player[g0 + gi], g_player[g0 + gj]
+                key = np.minimum(pi, pj) * n_src + np.maximum(pi, pj)
+                np.add.at(acc, key, val.T)
+        a = b
+
+    T = len(packed.cls_tree_offsets) - 1
+    scale = 1.0 if getattr(packed, "cls_kind", 0) == 1 else 1.0 / T
+    upper = (acc.T * scale).reshape(n_rows, n_src, n_src)
+    out = upper + upper.transpose(0, 2, 1)  # the diagonal of upper is zero
+    d = np.arange(n_src)
+    out[:, d, d] = phi - out.sum(axis=2)
+    return out
+
+
 def ishap_weight_table(n: int = N_CAT + N_NUM) -> np.ndarray:
     """W[a, b] = (a-1)! b! / (a+b)! for a >= 1 (row 0 is zero), f64[n+1, n+1]:
     the Shapley weight of a player that is one of ``a`` players on its own

@@ -138,7 +138,11 @@ class ExplainOutput(BaseModel):
     ``?method=interventional`` gives Shapley values of the interventional
     game against the model's background sample; ``base_value`` is then the
     mean model output over those rows and ``background_rows`` their number
-    (absent for the other methods)."""
+    (absent for the other methods).
+    ``?method=shap&interactions=true`` adds ``interactions``: per row the
+    symmetric 23 x 23 matrix of exact SHAP interaction values in ``features``
+    order on both axes, whose row r sums to ``contributions[r]`` (absent
+    otherwise)."""
 
     output_space: str
     base_value: float
@@ -148,6 +152,7 @@ class ExplainOutput(BaseModel):
     top_reasons: list[list[Reason]]
     method: str | None = None
     background_rows: int | None = None
+    interactions: list[list[list[float]]] | None = None
 
 
 # The one-record CI smoke-test fixture (reference app/sample-request.json).

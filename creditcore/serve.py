@@ -516,13 +516,16 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
         request: Request,
         top_k: int = Query(3, ge=0, le=len(FEATURES)),
         method: str | None = Query(None),
+        interactions: bool = Query(False),
     ):
         """Per-row feature attributions ("reason codes") for the classifier:
         prediction-path (Saabas) contributions per input feature by default,
         exact TreeSHAP values with ``?method=shap``, interventional Shapley
         values against the model's background sample with
         ``?method=interventional``, plus the up-to-top_k
-        features pushing each row toward default. One attempt on one live
+        features pushing each row toward default.
+        ``?method=shap&interactions=true`` adds the exact SHAP interaction
+        values, one 23 x 23 matrix per row. One attempt on one live
         replica; bypasses the micro-batcher."""
         import asyncio
 
@@ -532,6 +535,11 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
                 detail=f"method must be one of {list(EXPLAIN_METHODS)}",
             )
         use = method or "saabas"
+        if interactions and method != "shap":
+            raise HTTPException(
+                status_code=422,
+                detail="interactions=true needs method=shap",
+            )
 
         metrics: Metrics = state["metrics"]
         engines = state["engines"]
@@ -553,6 +561,12 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
             raise HTTPException(
                 status_code=413,
                 detail=f"/explain (method={use}) takes at most {max_rows} rows",
+            )
+        if interactions and len(codes) > ScoringEngine.INTERACTION_MAX_ROWS:
+            raise HTTPException(
+                status_code=413,
+                detail="/explain with interactions=true takes at most "
+                f"{ScoringEngine.INTERACTION_MAX_ROWS} rows",
             )
         if use == "shap" and engines[0].packed.cls_node_cover is None:
             raise HTTPException(
@@ -582,7 +596,7 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
         t0 = time.perf_counter()
         try:
             out = await asyncio.get_running_loop().run_in_executor(
-                None, engines[idx].explain_arrays, codes, nums, use
+                None, engines[idx].explain_arrays, codes, nums, use, None, interactions
             )
             pool.report_ok(idx)
         except ExplainUnavailable as e:
@@ -604,6 +618,8 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
             payload["method"] = method
         if "background_rows" in out:  # method=interventional only
             payload["background_rows"] = int(out["background_rows"])
+        if "interactions" in out:  # method=shap&interactions=true only
+            payload["interactions"] = out["interactions"].tolist()
         metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
         return _json_response(payload)
 

@@ -738,6 +738,189 @@ __global__ __launch_bounds__(CONTRIB_BLOCK) void forest_ishap_kernel(
   }
 }
 
+// Exact path-dependent SHAP interaction values over the same path table.
+// For one leaf with value v and distinct players p on its path (z_p, o_p as
+// in forest_shap_kernel), the Shapley interaction index of i != j is
+//
+//   Phi_ij = v/2 (o_i - z_i)(o_j - z_j) int_0^1 prod_{p != i,j} f_p(t) dt,
+//   f_p(t) = z_p (1-t) + o_p t
+//
+// (degree <= N_SRC - 2, the SHAP_NQ-point rule is exact). With f_pq, L_q as
+// above and g_pq = (o_p - z_p) / f_pq:  Phi_ij = v/2 sum_q w_q L_q g_iq g_jq.
+//   o_p = 0: g_pq = -1 / (1 - t_q), a constant table (z_p cancels; with
+//            z_p = 0, L_q is exactly 0 and so is every pair of the leaf);
+//   o_p = 1: g_pq = (1 - z_p) / f_pq depends on the path only and is computed
+//            once per path into LDS; exactly 0 when z_p = 1.
+// No 0/0 can form: f_pq >= t_q > 0 wherever a quotient is taken.
+//
+// A row needs 253 f64 accumulators (unordered player pairs), so the split is
+// not forest_shap_kernel's: a block stages SHAPI_ROWS = 16 rows column-major
+// with fused imputation and SHAPI_TPR = 16 threads serve each row
+// (tid = k * SHAPI_ROWS + row, so a wavefront holds all 16 rows x 4 values
+// of k and the rows of one k hit 16 consecutive doubles). Per path:
+//   1. every thread walks the records for its row -> o-mask; thread k <
+//      SHAP_NQ also carries the one product L_k and writes w_k L_k to LDS;
+//      the thread of row r keeps z of groups r and r + 16 and writes their
+//      g_pk afterwards (one or two divisions per thread, not one per group
+//      per wavefront); thread 0 writes the group -> player map;
+//   2. barrier; every thread takes the 12 w_q L_q of its row into registers
+//      and the m(m-1)/2 group pairs are dealt round-robin over k. The pair a
+//      thread handles in an iteration is block-uniform (s_pair decodes it),
+//      only the o-cases differ by row. Two groups of a path are different
+//      players and a pair has one owner k, so no two threads touch the same
+//      accumulator within a path;
+//   3. barrier (the next path rewrites the tables and may hand an
+//      accumulator to another thread of the row).
+// Both barriers sit in the path loop, whose trip count and skips (root leaf,
+// more than N_SRC groups: skipped, never indexed) are block-uniform; threads
+// past n_rows work on a clamped row and only skip the flush. The flush is
+// one atomicAdd per non-zero (row, pair) per block into the upper triangle;
+// the binding mirrors it (both sides bit-equal) and the diagonal is the
+// caller's (engine: phi_i minus the off-diagonal row sum).
+// LDS: 253*16*8 B accumulators 32,384 + rows 1,184 + w L 1,536 + g 2,208 +
+// g-off 96 + map 92 + pair table 506 = 38,006 B static (four blocks per CU).
+#define SHAPI_ROWS 16
+#define SHAPI_TPR 16
+#define SHAPI_BLOCK (SHAPI_ROWS * SHAPI_TPR)
+#define SHAPI_PAIRS (N_SRC * (N_SRC - 1) / 2)
+static_assert(SHAPI_TPR >= SHAP_NQ, "one thread of a row per quadrature node");
+static_assert(2 * SHAPI_ROWS >= N_SRC, "two group slots per row index cover a path");
+static_assert(N_SRC <= SHAPI_BLOCK, "the pair table is filled one column per thread");
+
+__global__ __launch_bounds__(SHAPI_BLOCK) void forest_shap_inter_kernel(
+    const short* __restrict__ codes,       // [B, N_CAT]
+    const float* __restrict__ nums,        // [B, N_NUM]
+    const float* __restrict__ medians,     // [N_NUM]
+    const float* __restrict__ leaf_value,  // [L]
+    const int* __restrict__ leaf_off,      // [L+1] into splits
+    const int4* __restrict__ splits,       // [S] {feat, thr bits, frac bits, flags}
+    int n_leaves,
+    int n_rows,
+    double half_scale,                     // (1/T or 1) / 2
+    double* __restrict__ inter)            // [B, N_SRC, N_SRC], pre-zeroed; upper triangle
+{
+  constexpr double T[SHAP_NQ] = {SHAP_T_LIST};
+  constexpr double W[SHAP_NQ] = {SHAP_W_LIST};
+
+  __shared__ double s_acc[SHAPI_PAIRS * SHAPI_ROWS];  // [hi(hi-1)/2 + lo][row]
+  __shared__ short s_codes[N_CAT * SHAPI_ROWS];
+  __shared__ float s_nums[N_NUM * SHAPI_ROWS];
+  __shared__ double s_wl[SHAP_NQ * SHAPI_ROWS];       // w_q L_q of each row
+  __shared__ double s_g[N_SRC * SHAP_NQ];             // g_pq for o_p = 1
+  __shared__ double s_goff[SHAP_NQ];                  // g_pq for o_p = 0
+  __shared__ int s_player[N_SRC];                     // player of each group
+  __shared__ unsigned short s_pair[SHAPI_PAIRS];      // b(b-1)/2 + a -> a | b << 8
+
+  const int tid = threadIdx.x;
+  const int ri = tid % SHAPI_ROWS;
+  const int k = tid / SHAPI_ROWS;
+  const int row_raw = blockIdx.x * SHAPI_ROWS + ri;
+  const bool live = row_raw < n_rows;
+  const int row = live ? row_raw : n_rows - 1;  // n_rows >= 1 (host)
+
+  for (int c = k; c < N_CAT; c += SHAPI_TPR)
+    s_codes[c * SHAPI_ROWS + ri] = codes[(size_t)row * N_CAT + c];
+  for (int c = k; c < N_NUM; c += SHAPI_TPR) {
+    const float v = nums[(size_t)row * N_NUM + c];
+    s_nums[c * SHAPI_ROWS + ri] = isnan(v) ? medians[c] : v;
+  }
+  for (int j = tid; j < SHAPI_PAIRS * SHAPI_ROWS; j += SHAPI_BLOCK) s_acc[j] = 0.0;
+  if (tid >= 1 && tid < N_SRC)
+    for (int a = 0; a < tid; ++a)
+      s_pair[tid * (tid - 1) / 2 + a] = (unsigned short)(a | (tid << 8));
+  double tk = 0.0, wk = 0.0;  // this thread's quadrature node
+#pragma unroll
+  for (int q = 0; q < SHAP_NQ; ++q)
+    if (k == q) {
+      tk = T[q];
+      wk = W[q];
+      if (ri == 0) s_goff[q] = -1.0 / (1.0 - T[q]);
+    }
+  __syncthreads();  // the staged rows are read across k
+
+  for (int leaf = blockIdx.y; leaf < n_leaves; leaf += gridDim.y) {
+    const int r0 = leaf_off[leaf];
+    const int r1 = leaf_off[leaf + 1];
+    if (r1 == r0) continue;  // root leaf: no players (block-uniform)
+
+    // pass 1: o-mask of the row, L_k, and z of the groups this thread owns
+    unsigned omask = 0;
+    int m = 0;  // player groups closed so far
+    double z = 1.0, lk = 1.0, z0 = 1.0, z1 = 1.0;
+    bool o = true;
+    for (int r = r0; r < r1; ++r) {
+      const int4 rec = splits[r];
+      const int player = (rec.w >> SHAP_PLAYER_SHIFT) & 0xFF;
+      const int code = (int)((unsigned)rec.w >> SHAP_CODE_SHIFT) - 1;
+      const float x =
+          (code >= 0) ? ((s_codes[player * SHAPI_ROWS + ri] == (short)code) ? 1.0f : 0.0f)
+                      : s_nums[(player - N_CAT) * SHAPI_ROWS + ri];
+      const bool right = !(x <= __int_as_float(rec.y));
+      o = o && (right == (bool)(rec.w & SHAP_DIR_RIGHT));
+      z *= (double)__int_as_float(rec.z);
+      const bool last = (r + 1 == r1) || (splits[r + 1].w & SHAP_FIRST);
+      if (last) {  // block-uniform
+        if (m < N_SRC) {
+          lk *= fma((o ? 1.0 : 0.0) - z, tk, z);
+          omask |= (o ? 1u : 0u) << m;
+          if (m == ri) z0 = z;
+          if (m == ri + SHAPI_ROWS) z1 = z;
+          if (tid == 0) s_player[m] = player;
+        }
+        ++m;
+        z = 1.0;
+        o = true;
+      }
+    }
+    // The host has checked the table (at most N_SRC groups per path); a
+    // path that breaks that is skipped, never indexed (block-uniform, and
+    // before this iteration's barriers).
+    if (m > N_SRC) continue;
+    if (k < SHAP_NQ) {
+      s_wl[k * SHAPI_ROWS + ri] = wk * lk;
+      if (ri < m)
+        s_g[ri * SHAP_NQ + k] = (1.0 - z0) / fma(1.0 - z0, tk, z0);  // f >= t_k > 0
+      if (ri + SHAPI_ROWS < m)
+        s_g[(ri + SHAPI_ROWS) * SHAP_NQ + k] = (1.0 - z1) / fma(1.0 - z1, tk, z1);
+    }
+    __syncthreads();  // s_wl, s_g, s_player complete
+
+    // pass 2: this thread's share of the path's group pairs
+    double wl[SHAP_NQ];
+#pragma unroll
+    for (int q = 0; q < SHAP_NQ; ++q) wl[q] = s_wl[q * SHAPI_ROWS + ri];
+    const double v = (double)leaf_value[leaf];
+    const int n_pairs = m * (m - 1) / 2;
+    for (int pr = k; pr < n_pairs; pr += SHAPI_TPR) {
+      const int ab = s_pair[pr];
+      const int a = ab & 0xFF;
+      const int b = ab >> 8;
+      const double* ga = ((omask >> a) & 1u) ? &s_g[a * SHAP_NQ] : s_goff;
+      const double* gb = ((omask >> b) & 1u) ? &s_g[b * SHAP_NQ] : s_goff;
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < SHAP_NQ; ++q) s = fma(wl[q] * ga[q], gb[q], s);
+      const int pa = s_player[a];
+      const int pb = s_player[b];
+      const int lo = min(pa, pb);
+      const int hi = max(pa, pb);
+      if (lo != hi)  // always, by the table's construction; keeps the index in range
+        s_acc[(hi * (hi - 1) / 2 + lo) * SHAPI_ROWS + ri] += v * s;
+    }
+    __syncthreads();  // the next path rewrites the tables
+  }
+
+  if (!live) return;
+  double* out = inter + (size_t)row * N_SRC * N_SRC;
+  for (int pr = k; pr < SHAPI_PAIRS; pr += SHAPI_TPR) {
+    const double acc = s_acc[pr * SHAPI_ROWS + ri];
+    if (acc != 0.0) {
+      const int ab = s_pair[pr];
+      atomicAdd(&out[(ab & 0xFF) * N_SRC + (ab >> 8)], acc * half_scale);
+    }
+  }
+}
+
 // 4-tree ILP + optional transposed grid (blockIdx.x = tree chunk so the
 // dispatcher's id%8 XCD placement gives adjacent chunks to different XCDs,
 // keeping each XCD's L2 on a tree subset). Experimental A/B variants.
@@ -1326,14 +1509,13 @@ torch::Tensor forest_contrib(
   return contrib;
 }
 
-// Exact TreeSHAP values f64[B, 23] for the classifier forest
-// (forest_shap_kernel) from the path table of pack.build_shap_paths.
-// Stateless like forest_contrib; the caller has bounds-checked the table.
-torch::Tensor forest_shap(
-    torch::Tensor codes, torch::Tensor nums,
-    torch::Tensor leaf_value, torch::Tensor leaf_off, torch::Tensor splits,
-    torch::Tensor medians, int64_t cls_kind, int64_t n_trees,
-    int64_t block_target)
+// Host-side checks shared by the path-table attributions (forest_shap,
+// forest_shap_interactions): inputs and table on one GPU, dtypes, shapes.
+static void check_shap_inputs(
+    const torch::Tensor& codes, const torch::Tensor& nums,
+    const torch::Tensor& leaf_value, const torch::Tensor& leaf_off,
+    const torch::Tensor& splits, const torch::Tensor& medians,
+    int64_t n_trees, int64_t block_target)
 {
   check_inputs(codes, nums);
   TORCH_CHECK(block_target >= 1 && block_target <= 65535, "bad block_target");
@@ -1354,6 +1536,19 @@ torch::Tensor forest_shap(
   TORCH_CHECK(splits.dim() == 2 && splits.size(1) == 4, "splits must be [S, 4]");
   TORCH_CHECK(medians.numel() == N_NUM, "medians must have N_NUM entries");
   TORCH_CHECK(n_trees >= 1, "forest has no trees");
+}
+
+// Exact TreeSHAP values f64[B, 23] for the classifier forest
+// (forest_shap_kernel) from the path table of pack.build_shap_paths.
+// Stateless like forest_contrib; the caller has bounds-checked the table.
+torch::Tensor forest_shap(
+    torch::Tensor codes, torch::Tensor nums,
+    torch::Tensor leaf_value, torch::Tensor leaf_off, torch::Tensor splits,
+    torch::Tensor medians, int64_t cls_kind, int64_t n_trees,
+    int64_t block_target)
+{
+  check_shap_inputs(codes, nums, leaf_value, leaf_off, splits, medians, n_trees,
+                    block_target);
 
   c10::hip::HIPGuard guard((c10::DeviceIndex)codes.get_device());
   const int B = (int)codes.size(0);
@@ -1376,6 +1571,44 @@ torch::Tensor forest_shap(
       shap.data_ptr<double>());
   HIP_CHECK(hipGetLastError());
   return shap;
+}
+
+// Exact SHAP interaction values f64[B, 23, 23] for the classifier forest
+// (forest_shap_inter_kernel) from the same path table: symmetric, each
+// off-diagonal entry half of the pair's interaction index, the diagonal
+// left at zero for the caller (engine: phi_i minus the off-diagonal row sum).
+// Stateless like forest_shap; the caller has bounds-checked the table.
+torch::Tensor forest_shap_interactions(
+    torch::Tensor codes, torch::Tensor nums,
+    torch::Tensor leaf_value, torch::Tensor leaf_off, torch::Tensor splits,
+    torch::Tensor medians, int64_t cls_kind, int64_t n_trees,
+    int64_t block_target)
+{
+  check_shap_inputs(codes, nums, leaf_value, leaf_off, splits, medians, n_trees,
+                    block_target);
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)codes.get_device());
+  const int B = (int)codes.size(0);
+  const int L = (int)leaf_value.size(0);
+  auto upper = torch::zeros({B, N_SRC, N_SRC},
+      torch::TensorOptions().dtype(torch::kFloat64).device(codes.device()));
+  if (B == 0 || L == 0) return upper;
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  const int row_blocks = ceil_div(B, SHAPI_ROWS);
+  // forest_shap's grid rule: path-chunks fill the CUs at small B; every
+  // chunk ends in up to 253 atomics per row
+  const int chunks = std::max(1, std::min(ceil_div((int)block_target, row_blocks), L));
+  const double scale = (cls_kind == 1) ? 1.0 : 1.0 / (double)n_trees;
+  hipLaunchKernelGGL(forest_shap_inter_kernel, dim3(row_blocks, chunks),
+      dim3(SHAPI_BLOCK), 0, stream,
+      codes.data_ptr<short>(), nums.data_ptr<float>(), medians.data_ptr<float>(),
+      leaf_value.data_ptr<float>(), leaf_off.data_ptr<int>(),
+      reinterpret_cast<const int4*>(splits.data_ptr<int>()), L, B, 0.5 * scale,
+      upper.data_ptr<double>());
+  HIP_CHECK(hipGetLastError());
+  // the kernel fills the strict upper triangle; x + x^T is bit-symmetric
+  return upper + upper.transpose(1, 2);
 }
 
 // Interventional Shapley values f64[B, 23] of the classifier forest against
@@ -4025,6 +4258,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("leaf_off"), py::arg("splits"), py::arg("medians"),
         py::arg("cls_kind"), py::arg("n_trees"),
         py::arg("block_target") = 2048);
+  m.def("forest_shap_interactions", &forest_shap_interactions,
+        "Per-row exact SHAP interaction values f64[B,23,23], diagonal left "
+        "at zero (gfx950)",
+        py::arg("codes"), py::arg("nums"), py::arg("leaf_value"),
+        py::arg("leaf_off"), py::arg("splits"), py::arg("medians"),
+        py::arg("cls_kind"), py::arg("n_trees"),
+        py::arg("block_target") = 2048);
+  m.attr("SHAP_INTER_ROWS_PER_BLOCK") = py::int_(SHAPI_ROWS);
   m.def("forest_ishap", &forest_ishap,
         "Per-row interventional Shapley values f64[B,23] against a "
         "background sample (gfx950)",
