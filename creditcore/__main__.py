@@ -7,6 +7,7 @@ Replaces the reference's Databricks bundle + GitHub Actions + Bicep pipeline
     python -m creditcore pack   --model-dir ./model --out ./model/packed.npz
     python -m creditcore serve  [--model-directory ./model] [--port 5000] ...
     python -m creditcore smoke  [--url http://127.0.0.1:5000]
+    python -m creditcore pdp    --model-directory ./model --features credit_limit,age --out pdp.json
 """
 
 from __future__ import annotations
@@ -240,6 +241,56 @@ def _cmd_score_batch(argv):
                       "engines": len(engines), "device": device}))
 
 
+def _cmd_pdp(argv):
+    """Offline model-validation artefact: partial dependence (and ICE curves
+    with --kind both) of a packaged model, written as JSON."""
+    p = argparse.ArgumentParser(prog="creditcore pdp")
+    p.add_argument("--model-directory", default="./model")
+    p.add_argument("--features", required=True,
+                   help="comma-separated entries: a feature name, or "
+                        "name:name for a two-way curve "
+                        "(credit_limit,age,credit_limit:age)")
+    p.add_argument("--data", default=None,
+                   help="CSV rows (the train --data schema) that replace the "
+                        "model's packed background sample; at most 1024 rows")
+    p.add_argument("--grid-resolution", type=int, default=20)
+    p.add_argument("--kind", default="average", choices=["average", "both"])
+    p.add_argument("--response", default="probability", choices=["probability", "raw"])
+    p.add_argument("--device", default="auto")
+    p.add_argument("--out", required=True)
+    a = p.parse_args(argv)
+    from .engine import load_engine
+    from .pack import encode_batch
+
+    features = []
+    for item in a.features.split(","):
+        names = tuple(n.strip() for n in item.split(":"))
+        features.append(names[0] if len(names) == 1 else names)
+    eng = load_engine(a.model_directory, device=a.device)
+    sample = None
+    if a.data:
+        import pandas as pd
+
+        sample = encode_batch(pd.read_csv(a.data), eng.packed.vocabs)
+    out = eng.partial_dependence(
+        features, sample=sample, grid_resolution=a.grid_resolution,
+        kind=a.kind, response=a.response,
+    )
+    doc = {
+        "output_space": out["output_space"],
+        "sample_rows": int(out["sample_rows"]),
+        "kind": a.kind,
+        "results": [
+            {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in res.items()}
+            for res in out["results"]
+        ],
+    }
+    with open(a.out, "w") as f:
+        json.dump(doc, f)
+    print(json.dumps({"out": a.out, "entries": len(doc["results"]),
+                      "sample_rows": doc["sample_rows"], "device": eng.device}))
+
+
 def _cmd_generate_data(argv):
     """Write a UCI-shaped synthetic CSV (the reference's curated.csv analog,
     reference databricks/data/; the real UCI CSV is not available offline)."""
@@ -274,6 +325,7 @@ def main():
         "train-dense": _cmd_train_dense,
         "score-batch": _cmd_score_batch,
         "generate-data": _cmd_generate_data,
+        "pdp": _cmd_pdp,
     }
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         print(f"usage: python -m creditcore {{{'|'.join(cmds)}}} [args]", file=sys.stderr)

@@ -45,15 +45,16 @@ class ExplainTooLarge(ValueError):
 
 
 def _check_forest_tables(p: PackedModel) -> None:
-    """Host-side bounds check of everything forest_contrib_kernel indexes
-    with model data (the kernel trusts its tables): node features, child
-    links, the one-hot/numeric source columns and the value array length."""
+    """Host-side bounds check of everything forest_contrib_kernel and
+    forest_whatif_kernel index with model data (the kernels trust their
+    tables): node features, child links, the one-hot/numeric source columns
+    and, where the model carries one, the value array length."""
     nodes, off = p.cls_nodes, p.cls_tree_offsets
     n_feat = len(p.feat_col)
     ok = (
         nodes.ndim == 2
         and nodes.shape[1] == 4
-        and len(p.cls_node_value) == len(nodes)
+        and (p.cls_node_value is None or len(p.cls_node_value) == len(nodes))
         and len(p.feat_code) == n_feat
         and len(p.medians) == N_NUM
         and len(off) >= 2
@@ -164,6 +165,19 @@ class ScoringEngine:
     # profiles/bench_results/shap_inter_micro.txt. Every row count up to the
     # call cap is within the bound, so today no call is sliced.
     INTERACTION_LAUNCH_ROWS = 128
+    # partial_dependence: most (job, row) pairs of one forest_whatif launch
+    # (a job is one grid point's column override, a pair one walk of the
+    # whole forest); a call above it runs as several launches over job
+    # slices. Sized like ISHAP_MAX_PAIRS: the largest measured pair count
+    # whose launch on the flagship forest (RF 500 x depth 16) with the
+    # 256-row sample is no longer than 1.25 x the method="shap" launch at
+    # SHAP_MAX_ROWS measured in the same run: forest_shap at 1024 rows
+    # 60.34 ms (bound 75.43 ms), forest_whatif at 8192 jobs x 256 rows =
+    # 2,097,152 pairs 23.80 ms on an MI355X (the largest shape measured; the
+    # default request, 81,152 pairs, 3.46 ms),
+    # profiles/bench_results/pdp_micro.txt. The largest call the caps allow
+    # (10.7 M pairs) runs as six launches.
+    PDP_LAUNCH_PAIRS = 2097152
 
     def __init__(
         self,
@@ -188,6 +202,7 @@ class ScoringEngine:
         # its base value, and its device copy
         self._ishap = None
         self._ishap_dev = None
+        self._pdp_sample_dev = None  # partial_dependence: the packed sample
         if device == "cuda":
             self._init_gpu()
 
@@ -362,35 +377,7 @@ class ScoringEngine:
         # The lock covers the lazy upload and the call: concurrent explains on
         # one replica serialize; scoring is untouched (no shared state).
         with self._explain_lock:
-            m = self._explain_dev
-            if m is None:
-                p = self.packed
-                _check_forest_tables(p)
-                # Own device copies of the model tensors — the session keeps
-                # its buffers private, so cls_nodes sits in HBM twice
-                # (16 B/node; accepted for an explain path that never
-                # touches session state).
-                m = {
-                    "cls_nodes": torch.from_numpy(
-                        np.ascontiguousarray(p.cls_nodes, dtype=np.int32)
-                    ).to(dev),
-                    "cls_node_value": torch.from_numpy(
-                        np.ascontiguousarray(p.cls_node_value, dtype=np.float32)
-                    ).to(dev),
-                    "cls_off": torch.from_numpy(
-                        np.ascontiguousarray(p.cls_tree_offsets, dtype=np.int32)
-                    ).to(dev),
-                    "feat_col": torch.from_numpy(
-                        np.ascontiguousarray(p.feat_col, dtype=np.int32)
-                    ).to(dev),
-                    "feat_code": torch.from_numpy(
-                        np.ascontiguousarray(p.feat_code, dtype=np.int32)
-                    ).to(dev),
-                    "medians": torch.from_numpy(
-                        np.ascontiguousarray(p.medians, dtype=np.float32)
-                    ).to(dev),
-                }
-                self._explain_dev = m
+            m = self._forest_dev()
             with torch.cuda.device(dev):
                 out = ext.forest_contrib(
                     torch.from_numpy(codes).to(dev),
@@ -404,6 +391,36 @@ class ScoringEngine:
                     int(getattr(self.packed, "cls_kind", 0)),
                 )
                 return out.cpu().numpy()  # D2H copy synchronizes the stream
+
+    def _forest_dev(self) -> dict:
+        """The classifier forest tables on the device, bounds-checked and
+        uploaded once; the caller holds _explain_lock."""
+        import torch
+
+        m = self._explain_dev
+        if m is None:
+            p = self.packed
+            dev = torch.device("cuda", self.device_index)
+            _check_forest_tables(p)
+            # Own device copies of the model tensors — the session keeps
+            # its buffers private, so cls_nodes sits in HBM twice
+            # (16 B/node; accepted for an explain path that never
+            # touches session state).
+            tables = [
+                ("cls_nodes", p.cls_nodes, np.int32),
+                ("cls_off", p.cls_tree_offsets, np.int32),
+                ("feat_col", p.feat_col, np.int32),
+                ("feat_code", p.feat_code, np.int32),
+                ("medians", p.medians, np.float32),
+            ]
+            if p.cls_node_value is not None:  # Saabas only
+                tables.append(("cls_node_value", p.cls_node_value, np.float32))
+            m = {
+                k: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+                for k, a, dt in tables
+            }
+            self._explain_dev = m
+        return m
 
     def _explain_shap(
         self, codes: np.ndarray, nums: np.ndarray, interactions: bool = False
@@ -647,6 +664,145 @@ class ScoringEngine:
                 int(self.packed.cls_n_trees),
             )
             return out.cpu().numpy()  # D2H copy synchronizes the stream
+
+    # ------------------------------------------------- partial dependence
+    def partial_dependence(
+        self,
+        features,
+        sample=None,
+        grid_resolution: int = 20,
+        percentiles=(0.05, 0.95),
+        grid: dict | None = None,
+        kind: str = "average",
+        response: str = "probability",
+    ) -> dict:
+        """Partial dependence (and, with ``kind="both"``, the per-row ICE
+        curves) of the classifier output on one feature or a pair: every row
+        of a sample is scored with the feature set to each grid value in
+        turn, and the outputs are averaged over the rows.
+
+        ``features`` lists feature names (one-way) and pairs of distinct
+        names (two-way). ``sample`` is an encoded ``(codes, nums)`` pair and
+        defaults to the packed background sample. Grids follow the rule of
+        creditcore/pdp.py (scikit-learn's, f32-rounded; categoricals take the
+        whole vocabulary) unless ``grid={name: values}`` gives them.
+        ``response="raw"`` (gradient boosting only) returns log-odds, not
+        probabilities; a probability is taken per (row, grid point) before
+        the rows are averaged, as scikit-learn's predict_proba PDP does.
+
+        Returns ``{"results": [...], "sample_rows", "output_space"}``; each
+        result holds ``features``, ``grid_values`` (one list per axis),
+        ``average`` f64[G] or f64[G0, G1] and, with ``kind="both"``,
+        ``individual`` f64[R, G] or f64[R, G0, G1]. The scoring session is not
+        touched. Caps (creditcore/pdp.py) raise ExplainTooLarge."""
+        from . import pdp
+
+        p = self.packed
+        if kind not in pdp.PDP_KINDS:
+            raise ValueError(f"kind must be one of {pdp.PDP_KINDS} (got {kind!r})")
+        if response not in pdp.PDP_RESPONSES:
+            raise ValueError(f"response must be one of {pdp.PDP_RESPONSES} (got {response!r})")
+        cls_kind = int(getattr(p, "cls_kind", 0))
+        if response == "raw" and cls_kind != 1:
+            raise ValueError("response='raw' applies to the log-odds (boosted) families only")
+        own = sample is None  # the packed sample: its device copy is kept
+        try:
+            entries = pdp.parse_features(features)
+            res, pct = pdp.check_grid_args(grid_resolution, percentiles)
+            overrides = pdp.check_grid_override(grid)
+            if own:
+                if p.bg_codes is None or p.bg_nums is None:
+                    raise ExplainUnavailable(
+                        "model was packed without a background sample; re-train "
+                        "and re-pack it (or pass sample=) to enable partial dependence"
+                    )
+                sample = (p.bg_codes, p.bg_nums)
+            codes = np.ascontiguousarray(sample[0], dtype=np.int16)
+            nums = np.ascontiguousarray(sample[1], dtype=np.float32)
+            r = len(codes)
+            if codes.shape != (r, N_CAT) or nums.shape != (r, N_NUM):
+                raise ValueError(f"sample must be (codes [R, {N_CAT}], nums [R, {N_NUM}])")
+            if r < 1:
+                raise ValueError("the sample must have at least one row")
+            if r > pdp.PDP_MAX_ROWS:
+                raise pdp.PdpTooLarge(
+                    f"the sample is capped at {pdp.PDP_MAX_ROWS} rows (got {r})"
+                )
+            nums_imp = cpu_ref.impute_nums(p, nums)
+            axes: dict = {}
+            for names in entries:
+                for n in names:
+                    if n not in axes:
+                        axes[n] = pdp.build_axis(
+                            n, p.vocabs, nums_imp, res, pct, overrides.get(n)
+                        )
+            tables = [pdp.entry_jobs([axes[n] for n in names]) for names in entries]
+        except pdp.PdpTooLarge as e:
+            raise ExplainTooLarge(str(e)) from None
+        jobs = np.ascontiguousarray(np.concatenate(tables), dtype=np.int32)
+        # One launch covers at most PDP_LAUNCH_PAIRS (job, row) pairs; a
+        # larger call goes job slice by job slice.
+        step = max(1, int(self.PDP_LAUNCH_PAIRS) // r)
+        with self._explain_lock:
+            if self.device == "cuda":
+                run = self._whatif_gpu(codes, nums, own)
+            else:
+                def run(jb):
+                    return cpu_ref.forest_whatif_cpu(p, codes, nums_imp, jb)
+            raw = np.concatenate(
+                [run(jobs[s : s + step]) for s in range(0, len(jobs), step)]
+            )
+        vals = pdp.finalize(raw, cls_kind, float(p.cls_bias), int(p.cls_n_trees), response)
+        results, at = [], 0
+        for names, table in zip(entries, tables):
+            shape = [len(axes[n].bits) for n in names]
+            v = vals[at : at + len(table)]  # [G, R], axis 0 of a pair major
+            at += len(table)
+            out = {
+                "features": list(names),
+                "grid_values": [list(axes[n].values) for n in names],
+                "average": v.mean(axis=1).reshape(shape),
+            }
+            if kind == "both":
+                out["individual"] = np.ascontiguousarray(v.T).reshape([r] + shape)
+            results.append(out)
+        return {
+            "results": results,
+            "sample_rows": r,
+            "output_space": "log_odds" if response == "raw" else "probability",
+        }
+
+    def _whatif_gpu(self, codes: np.ndarray, nums: np.ndarray, own: bool):
+        """One-launch runner of forest_whatif on the device (job table in, raw
+        f64[J, R] sums out); the caller holds _explain_lock. Uses the
+        lazily uploaded forest tables of _explain_gpu; the packed sample's
+        device copy is kept, another sample is uploaded per call."""
+        import torch
+
+        ext = self._gpu["ext"]
+        dev = torch.device("cuda", self.device_index)
+        m = self._forest_dev()
+        smp = self._pdp_sample_dev if own else None
+        if smp is None:
+            smp = (torch.from_numpy(codes).to(dev), torch.from_numpy(nums).to(dev))
+            if own:
+                self._pdp_sample_dev = smp
+
+        def run(jb: np.ndarray) -> np.ndarray:
+            with torch.cuda.device(dev):
+                out = ext.forest_whatif(
+                    smp[0],
+                    smp[1],
+                    m["cls_nodes"],
+                    m["cls_off"],
+                    m["feat_col"],
+                    m["feat_code"],
+                    m["medians"],
+                    torch.from_numpy(np.ascontiguousarray(jb, dtype=np.int32)),
+                )
+                return out.cpu().numpy()  # D2H copy synchronizes the stream
+
+        return run
 
     def explain_records(
         self,

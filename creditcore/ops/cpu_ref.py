@@ -26,8 +26,13 @@ def _traverse_forest(
     offsets: np.ndarray,
     value_of: "callable",
     n_rows: int,
+    tree_order: bool = False,
 ) -> np.ndarray:
-    """Sum of leaf values over all trees, per row.
+    """Sum of leaf values over all trees, per row. ``tree_order`` adds the
+    leaves of a row strictly in tree order (tree 0 first) and not in the
+    order the walks end, which is the sum a thread that owns all trees of a
+    row computes (forest_whatif_kernel): bit-identical, and monotone in a
+    feature wherever every tree is.
 
     Level-synchronous and vectorised over ALL (tree, row) pairs at once:
     every pair advances one node per iteration, so the loop count is the
@@ -41,6 +46,7 @@ def _traverse_forest(
     base = cur.copy()
     rows = np.tile(np.arange(n_rows, dtype=np.int64), T)
     acc = np.zeros(n_rows, dtype=np.float64)
+    leaf_of = np.zeros(T * n_rows, dtype=np.float64) if tree_order else None
     alive = np.arange(T * n_rows, dtype=np.int64)
     while len(alive):
         nidx = cur[alive]
@@ -48,7 +54,10 @@ def _traverse_forest(
         leaf = feat < 0
         if leaf.any():
             done = alive[leaf]
-            np.add.at(acc, rows[done], bits[cur[done]].astype(np.float64))
+            if tree_order:
+                leaf_of[done] = bits[cur[done]].astype(np.float64)
+            else:
+                np.add.at(acc, rows[done], bits[cur[done]].astype(np.float64))
             alive = alive[~leaf]
             if not len(alive):
                 break
@@ -58,6 +67,9 @@ def _traverse_forest(
         go_left = v <= bits[nidx]
         nxt = np.where(go_left, nodes[nidx, 2], nodes[nidx, 3])
         cur[alive] = base[alive] + nxt  # children are tree-relative
+    if tree_order:
+        for per_tree in leaf_of.reshape(T, n_rows):
+            acc += per_tree
     return acc
 
 
@@ -65,6 +77,18 @@ def score_forest_cpu(
     packed: PackedModel, codes: np.ndarray, nums_imp: np.ndarray
 ) -> np.ndarray:
     """Classifier P(default) per row = mean of leaf class-1 fractions."""
+    s = forest_raw_cpu(packed, codes, nums_imp)
+    if getattr(packed, "cls_kind", 0) == 1:  # gradient-boosted: logit sum
+        return 1.0 / (1.0 + np.exp(-(s + packed.cls_bias)))
+    return (s / packed.cls_n_trees).astype(np.float64)
+
+
+def forest_raw_cpu(
+    packed: PackedModel, codes: np.ndarray, nums_imp: np.ndarray, tree_order: bool = False
+) -> np.ndarray:
+    """Raw classifier sum per row, f64[B]: the leaf payloads over all trees,
+    before score_forest_cpu's 1/T or bias + sigmoid (``tree_order``:
+    _traverse_forest)."""
     fc, fk = packed.feat_col, packed.feat_code
 
     def value_of(rows: np.ndarray, feats: np.ndarray) -> np.ndarray:
@@ -78,10 +102,58 @@ def score_forest_cpu(
             v[~cat] = nums_imp[rows[~cat], col[~cat]]
         return v
 
-    s = _traverse_forest(packed.cls_nodes, packed.cls_tree_offsets, value_of, len(codes))
-    if getattr(packed, "cls_kind", 0) == 1:  # gradient-boosted: logit sum
-        return 1.0 / (1.0 + np.exp(-(s + packed.cls_bias)))
-    return (s / packed.cls_n_trees).astype(np.float64)
+    return _traverse_forest(
+        packed.cls_nodes, packed.cls_tree_offsets, value_of, len(codes), tree_order
+    )
+
+
+def forest_whatif_cpu(
+    packed: PackedModel,
+    codes: np.ndarray,
+    nums_imp: np.ndarray,
+    jobs: np.ndarray,
+    max_pairs: int = 1 << 21,
+) -> np.ndarray:
+    """What-if raw classifier sums, f64[J, R]: row r of the (imputed) sample
+    with job j's overrides applied, summed over all trees in tree order
+    (forest_raw_cpu with ``tree_order``), as forest_whatif_kernel sums them.
+
+    ``jobs`` is i32[J, 4] {player0, bits0, player1, bits1}: player is the
+    schema feature index (0..N_CAT-1 categorical columns, N_CAT.. numerics;
+    -1 in slot 1 = no second override), bits the category code or the f32 bit
+    pattern of the value. Deliberately the dumb version: per job, copy the
+    sample, write the override into the column and run the scorer's own
+    traversal on the copy. Jobs are only stacked into one traversal call so
+    long as it stays under ``max_pairs`` (row, tree) pairs."""
+    jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, 4)
+    codes = np.ascontiguousarray(codes, dtype=np.int16)
+    nums_imp = np.ascontiguousarray(nums_imp, dtype=np.float32)
+    n_jobs, r = len(jobs), len(codes)
+    n_src = N_CAT + N_NUM
+    p0, p1 = jobs[:, 0], jobs[:, 2]
+    if n_jobs < 1 or r < 1:
+        raise ValueError("forest_whatif needs at least one job and one row")
+    if ((p0 < 0) | (p0 >= n_src) | (p1 < -1) | (p1 >= n_src) | (p0 == p1)).any():
+        raise ValueError("job players must be in range and distinct")
+    out = np.empty((n_jobs, r), dtype=np.float64)
+    step = max(1, max_pairs // max(1, r * packed.cls_n_trees))
+    for a in range(0, n_jobs, step):
+        chunk = jobs[a : a + step]
+        c = np.tile(codes, (len(chunk), 1))
+        x = np.tile(nums_imp, (len(chunk), 1))
+        for k, job in enumerate(chunk):
+            rows = slice(k * r, (k + 1) * r)
+            for player, bits in ((job[0], job[1]), (job[2], job[3])):
+                if player < 0:
+                    continue
+                if player < N_CAT:
+                    c[rows, player] = np.int16(bits)
+                else:
+                    x[rows, player - N_CAT] = np.int32(bits).view(np.float32)
+        out[a : a + len(chunk)] = forest_raw_cpu(packed, c, x, tree_order=True).reshape(
+            len(chunk), r
+        )
+    return out
 
 
 def forest_contrib_cpu(

@@ -155,6 +155,45 @@ class ExplainOutput(BaseModel):
     interactions: list[list[list[float]]] | None = None
 
 
+class PdpRequest(BaseModel):
+    """POST /explain/pdp request. ``features`` entries are a feature name
+    (one-way) or a pair of distinct names (two-way); ``grid`` optionally
+    replaces the grid of a feature (numbers for a numeric feature, known
+    categories for a categorical one)."""
+
+    features: list[str | list[str]]
+    grid_resolution: int = 20
+    percentiles: list[float] = [0.05, 0.95]
+    kind: str = "average"
+    response: str = "probability"
+    grid: dict[str, list[float | str]] | None = None
+
+    model_config = ConfigDict(extra="ignore")
+
+
+class PdpCurve(BaseModel):
+    """Partial dependence of the classifier on one feature or a pair.
+    ``grid_values`` holds one list per axis (numbers, or category strings);
+    ``average`` is indexed [g] or [g0][g1]; ``individual`` (the ICE curves,
+    ``kind="both"`` only) is indexed [row][g] or [row][g0][g1]."""
+
+    features: list[str]
+    grid_values: list[list[float | str]]
+    average: list[float] | list[list[float]]
+    individual: list[list[float]] | list[list[list[float]]] | None = None
+
+
+class PdpOutput(BaseModel):
+    """POST /explain/pdp response: one curve per requested entry, computed on
+    the model's ``sample_rows`` background rows, in ``output_space``
+    ("probability", or "log_odds" with ``response="raw"``)."""
+
+    output_space: str
+    sample_rows: int
+    kind: str
+    results: list[PdpCurve]
+
+
 # The one-record CI smoke-test fixture (reference app/sample-request.json).
 SAMPLE_REQUEST: list[dict] = [
     {

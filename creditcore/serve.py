@@ -28,9 +28,22 @@ from fastapi import FastAPI, HTTPException, Query, Request, Response
 
 from .config import ServeConfig
 from .batching import MicroBatcher
-from .engine import EXPLAIN_METHODS, ExplainUnavailable, ScoringEngine, load_engine
+from .engine import (
+    EXPLAIN_METHODS,
+    ExplainTooLarge,
+    ExplainUnavailable,
+    ScoringEngine,
+    load_engine,
+)
 from .pack import encode_batch
-from .schema import FEATURES, ExplainOutput, LoanApplicant, ModelOutput
+from .schema import (
+    FEATURES,
+    ExplainOutput,
+    LoanApplicant,
+    ModelOutput,
+    PdpOutput,
+    PdpRequest,
+)
 from .utils import logging as reqlog
 from .utils.metrics import Metrics
 
@@ -621,6 +634,75 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
         if "interactions" in out:  # method=shap&interactions=true only
             payload["interactions"] = out["interactions"].tolist()
         metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
+        return _json_response(payload)
+
+    @app.post("/explain/pdp", response_model=PdpOutput)
+    async def explain_pdp(req: PdpRequest):
+        """Partial dependence (and, with ``kind="both"``, per-row ICE curves)
+        of the classifier on single features and pairs, computed on the
+        model's packed background sample: every sample row is scored with the
+        feature moved over a grid, and the outputs are averaged. One attempt
+        on one live replica; bypasses the micro-batcher."""
+        import asyncio
+
+        metrics: Metrics = state["metrics"]
+        engines = state["engines"]
+        pool: ReplicaPool = state["pool"]
+        packed = engines[0].packed
+        if packed.bg_codes is None or packed.bg_nums is None:
+            raise HTTPException(
+                status_code=501,
+                detail="the served model was packed without a background sample; "
+                "re-train and re-pack it to enable /explain/pdp",
+            )
+        try:
+            idx = pool.pick()
+        except RuntimeError:
+            metrics.observe_error()
+            raise HTTPException(status_code=503, detail="no healthy replicas")
+        t0 = time.perf_counter()
+        features = [f if isinstance(f, str) else tuple(f) for f in req.features]
+
+        def call():
+            return engines[idx].partial_dependence(
+                features,
+                grid_resolution=req.grid_resolution,
+                percentiles=tuple(req.percentiles),
+                grid=req.grid,
+                kind=req.kind,
+                response=req.response,
+            )
+
+        try:
+            out = await asyncio.get_running_loop().run_in_executor(None, call)
+            pool.report_ok(idx)
+        except ExplainTooLarge as e:  # the request's fault, not the replica's
+            raise HTTPException(status_code=413, detail=str(e))
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        except ExplainUnavailable as e:
+            raise HTTPException(status_code=501, detail=str(e))
+        except Exception as e:
+            metrics.observe_error()
+            pool.report_fail(idx)
+            raise HTTPException(status_code=500, detail=f"partial dependence failed: {e}")
+        results = []
+        for res in out["results"]:
+            item = {
+                "features": res["features"],
+                "grid_values": res["grid_values"],
+                "average": res["average"].tolist(),
+            }
+            if "individual" in res:
+                item["individual"] = res["individual"].tolist()
+            results.append(item)
+        payload = {
+            "output_space": out["output_space"],
+            "sample_rows": int(out["sample_rows"]),
+            "kind": req.kind,
+            "results": results,
+        }
+        metrics.observe_request(int(out["sample_rows"]), (time.perf_counter() - t0) * 1e3)
         return _json_response(payload)
 
     @app.get("/healthz")

@@ -180,6 +180,26 @@ def fit_detectors(df: pd.DataFrame) -> tuple[TabularDriftDetector, IForestDetect
     return drift, outlier
 
 
+def _monotone_pdp(pipeline, drift, outlier, monotone: dict) -> dict:
+    """One-way partial dependence (average only) of every constrained feature
+    on the model's background sample, through the CPU reference: the curve
+    the registered model carries next to its ``monotone`` signs."""
+    from .engine import ScoringEngine
+    from .pack import PackedModel, pack_classifier_pipeline, pack_drift, pack_isolation_forest
+
+    c = pack_classifier_pipeline(pipeline)
+    packed = PackedModel(**c, **pack_isolation_forest(outlier), **pack_drift(drift, c["vocabs"]))
+    names = [str(n) for n in monotone]
+    out = ScoringEngine(packed, device="cpu").partial_dependence(names)
+    return {
+        res["features"][0]: {
+            "grid_values": res["grid_values"][0],
+            "average": res["average"].tolist(),
+        }
+        for res in out["results"]
+    }
+
+
 def train_and_register(
     model_dir: str = "./model",
     model_name: str = DEFAULT_MODEL_NAME,
@@ -225,6 +245,8 @@ def train_and_register(
             raise RuntimeError("the best model violates its monotone constraints")
         extra["monotone"] = dict(best.params["monotone"])
     drift, outlier = fit_detectors(df)
+    if monotone:
+        extra["monotone_pdp"] = _monotone_pdp(best.pipeline, drift, outlier, monotone)
     registry.save_pyfunc_model(
         model_dir,
         best.pipeline,

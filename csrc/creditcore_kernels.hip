@@ -921,6 +921,121 @@ __global__ __launch_bounds__(SHAPI_BLOCK) void forest_shap_inter_kernel(
   }
 }
 
+// What-if forest sums for partial dependence / ICE curves: the raw classifier
+// sum (leaf payloads over ALL trees, as forest_kernel<false> accumulates them)
+// of every sample row under every job's overrides. A job {player0, bits0,
+// player1, bits1} replaces one or two source columns of the row: player is
+// the schema feature index of the attribution kernels (0..N_CAT-1 the
+// categorical columns, N_CAT..N_SRC-1 the numerics, -1 = no override, slot 1
+// only); bits is the category code, or the f32 bit pattern of the value. An
+// overridden numeric takes the job's value even where the row holds NaN; an
+// overridden categorical answers every one-hot test of its column.
+//
+// One thread per row, one WAVE per block (WHATIF_BLOCK = 64): rows staged
+// column-major in LDS with fused imputation exactly as forest_kernel, 74 B per
+// row, each thread touching only its own slots, so no barrier anywhere.
+// blockIdx.y strides over the jobs; per job the thread saves its own one or
+// two slots, writes the override, walks every tree and restores. One thread
+// owns all trees of a (job, row): the result is a plain store, deterministic,
+// no atomics, no pre-zeroed output. The walk keeps WHATIF_ILP consecutive
+// trees in flight (independent gather chains hide the node latency) and adds
+// their leaves afterwards in tree order, so the f64 sum is the tree-order sum
+// whatever the interleaving. Work per launch is jobs x rows threads; the
+// default call (256 rows, a few hundred jobs) is ~1600 one-wave blocks, which
+// spread over the 1024 SIMDs far more evenly than 400 four-wave blocks.
+#define WHATIF_BLOCK 64
+#define WHATIF_ILP 4
+
+__global__ __launch_bounds__(WHATIF_BLOCK) void forest_whatif_kernel(
+    const short* __restrict__ codes,    // [R, N_CAT]
+    const float* __restrict__ nums,     // [R, N_NUM], NaNs not yet imputed
+    const float* __restrict__ medians,  // [N_NUM]
+    const int4* __restrict__ nodes,     // [n_nodes] {feat, bits, left, right}
+    const int* __restrict__ tree_off,   // [T+1]
+    int n_trees,
+    const int* __restrict__ feat_col,   // [F]
+    const int* __restrict__ feat_code,  // [F]
+    const int4* __restrict__ jobs,      // [J] {player0, bits0, player1, bits1}
+    int n_jobs,
+    int n_rows,
+    double* __restrict__ out)           // [J, R]; every entry is written
+{
+  __shared__ short s_codes[N_CAT * WHATIF_BLOCK];
+  __shared__ float s_nums[N_NUM * WHATIF_BLOCK];
+
+  const int tid = threadIdx.x;
+  const int row = blockIdx.x * WHATIF_BLOCK + tid;
+  if (row >= n_rows) return;  // no barrier below: own LDS slots only
+
+#pragma unroll
+  for (int c = 0; c < N_CAT; ++c)
+    s_codes[c * WHATIF_BLOCK + tid] = codes[(size_t)row * N_CAT + c];
+#pragma unroll
+  for (int c = 0; c < N_NUM; ++c) {
+    const float v = nums[(size_t)row * N_NUM + c];
+    s_nums[c * WHATIF_BLOCK + tid] = isnan(v) ? medians[c] : v;
+  }
+
+  // Writes the override of one job slot into the thread's own LDS column and
+  // returns what stood there (as bits), for the restore. The host has checked
+  // the players; the unsigned compare also drops slot 1's -1.
+  auto swap_in = [&](int player, int bits) -> int {
+    int old = 0;
+    if ((unsigned)player < (unsigned)N_CAT) {
+      old = s_codes[player * WHATIF_BLOCK + tid];
+      s_codes[player * WHATIF_BLOCK + tid] = (short)bits;
+    } else if ((unsigned)player < (unsigned)N_SRC) {
+      old = __float_as_int(s_nums[(player - N_CAT) * WHATIF_BLOCK + tid]);
+      s_nums[(player - N_CAT) * WHATIF_BLOCK + tid] = __int_as_float(bits);
+    }
+    return old;
+  };
+
+  for (int j = blockIdx.y; j < n_jobs; j += gridDim.y) {
+    const int4 job = jobs[j];
+    const int old0 = swap_in(job.x, job.y);
+    const int old1 = swap_in(job.z, job.w);
+
+    double local = 0.0;
+    for (int t = 0; t < n_trees; t += WHATIF_ILP) {
+      int4 nd[WHATIF_ILP];
+      int base[WHATIF_ILP];
+#pragma unroll
+      for (int k = 0; k < WHATIF_ILP; ++k) {
+        base[k] = 0;
+        nd[k] = make_int4(-1, 0, 0, 0);  // past the last tree: a leaf of +0.0
+        if (t + k < n_trees) {
+          base[k] = tree_off[t + k];
+          nd[k] = nodes[base[k]];
+        }
+      }
+      bool any = true;
+      while (any) {
+        any = false;
+#pragma unroll
+        for (int k = 0; k < WHATIF_ILP; ++k) {
+          if (nd[k].x >= 0) {
+            const int col = feat_col[nd[k].x];
+            const int code = feat_code[nd[k].x];
+            const float v =
+                (code >= 0) ? ((s_codes[col * WHATIF_BLOCK + tid] == (short)code) ? 1.0f : 0.0f)
+                            : s_nums[col * WHATIF_BLOCK + tid];
+            nd[k] = nodes[base[k] + ((v <= __int_as_float(nd[k].y)) ? nd[k].z : nd[k].w)];
+            any = true;
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < WHATIF_ILP; ++k) local += (double)__int_as_float(nd[k].y);
+    }
+    out[(size_t)j * n_rows + row] = local;
+
+    // restore in reverse order (the host refuses player0 == player1 anyway)
+    swap_in(job.z, old1);
+    swap_in(job.x, old0);
+  }
+}
+
 // 4-tree ILP + optional transposed grid (blockIdx.x = tree chunk so the
 // dispatcher's id%8 XCD placement gives adjacent chunks to different XCDs,
 // keeping each XCD's L2 on a tree subset). Experimental A/B variants.
@@ -1507,6 +1622,84 @@ torch::Tensor forest_contrib(
       contrib.data_ptr<double>());
   HIP_CHECK(hipGetLastError());
   return contrib;
+}
+
+// What-if forest sums f64[J, R] for partial dependence (forest_whatif_kernel):
+// the raw classifier sum of each of the R sample rows under each of the J
+// jobs' overrides. `jobs` is a HOST i32[J, 4] table {player0, bits0, player1,
+// bits1}; it is checked here (players in range, distinct, category codes that
+// fit the i16 staging) and then copied to the device on the caller's stream.
+// Stateless like forest_contrib; the caller has bounds-checked the forest
+// tables (engine._check_forest_tables).
+torch::Tensor forest_whatif(
+    torch::Tensor codes, torch::Tensor nums,
+    torch::Tensor cls_nodes, torch::Tensor cls_off,
+    torch::Tensor feat_col, torch::Tensor feat_code,
+    torch::Tensor medians, torch::Tensor jobs, int64_t block_target)
+{
+  check_inputs(codes, nums);
+  TORCH_CHECK(block_target >= 1 && block_target <= 65535, "bad block_target");
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType st, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == codes.device(), name,
+                " must be on the inputs' GPU");
+    TORCH_CHECK(t.scalar_type() == st && t.is_contiguous(), name,
+                " has the wrong dtype or is not contiguous");
+  };
+  on_dev(nums, torch::kFloat32, "nums");
+  on_dev(cls_nodes, torch::kInt32, "cls_nodes");
+  on_dev(cls_off, torch::kInt32, "cls_off");
+  on_dev(feat_col, torch::kInt32, "feat_col");
+  on_dev(feat_code, torch::kInt32, "feat_code");
+  on_dev(medians, torch::kFloat32, "medians");
+  TORCH_CHECK(cls_nodes.dim() == 2 && cls_nodes.size(1) == 4, "cls_nodes must be [n, 4]");
+  TORCH_CHECK(feat_col.numel() == feat_code.numel(), "feat_col/feat_code size mismatch");
+  TORCH_CHECK(medians.numel() == N_NUM, "medians must have N_NUM entries");
+  TORCH_CHECK(cls_off.numel() >= 2, "forest has no trees");
+  TORCH_CHECK(!jobs.is_cuda() && jobs.scalar_type() == torch::kInt32 &&
+              jobs.is_contiguous() && jobs.dim() == 2 && jobs.size(1) == 4,
+              "jobs must be a contiguous host int32 [J, 4] table");
+
+  const int64_t J = jobs.size(0);
+  const int64_t R = codes.size(0);
+  TORCH_CHECK(J >= 1, "forest_whatif needs at least one job");
+  TORCH_CHECK(R >= 1, "forest_whatif needs at least one sample row");
+  TORCH_CHECK(J < (int64_t(1) << 31) && R < (int64_t(1) << 31), "too many jobs or rows");
+  const int* jb = jobs.data_ptr<int>();
+  auto code_ok = [](int player, int bits) {
+    return player >= N_CAT || (bits >= -32768 && bits <= 32767);
+  };
+  for (int64_t j = 0; j < J; ++j) {
+    const int p0 = jb[4 * j], p1 = jb[4 * j + 2];
+    TORCH_CHECK(p0 >= 0 && p0 < N_SRC, "job ", j, ": player0 out of range");
+    TORCH_CHECK(p1 >= -1 && p1 < N_SRC, "job ", j, ": player1 out of range");
+    TORCH_CHECK(p0 != p1, "job ", j, ": player0 and player1 must differ");
+    TORCH_CHECK(code_ok(p0, jb[4 * j + 1]) && (p1 < 0 || code_ok(p1, jb[4 * j + 3])),
+                "job ", j, ": category code does not fit int16");
+  }
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)codes.get_device());
+  auto out = torch::empty({J, R},
+      torch::TensorOptions().dtype(torch::kFloat64).device(codes.device()));
+  auto jobs_dev = jobs.to(codes.device());
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  const int T = (int)cls_off.size(0) - 1;
+  const int row_blocks = ceil_div((int)R, WHATIF_BLOCK);
+  // One-wave blocks; a block takes more than one job only once the grid
+  // passes block_target blocks (restaging 74 B per row is nothing next to a
+  // forest walk, and more blocks balance better).
+  const int chunks = (int)std::max<int64_t>(
+      1, std::min<int64_t>(ceil_div((int)block_target, row_blocks), J));
+  hipLaunchKernelGGL(forest_whatif_kernel, dim3(row_blocks, chunks),
+      dim3(WHATIF_BLOCK), 0, stream,
+      codes.data_ptr<short>(), nums.data_ptr<float>(), medians.data_ptr<float>(),
+      reinterpret_cast<const int4*>(cls_nodes.data_ptr<int>()),
+      cls_off.data_ptr<int>(), T,
+      feat_col.data_ptr<int>(), feat_code.data_ptr<int>(),
+      reinterpret_cast<const int4*>(jobs_dev.data_ptr<int>()), (int)J, (int)R,
+      out.data_ptr<double>());
+  HIP_CHECK(hipGetLastError());
+  return out;
 }
 
 // Host-side checks shared by the path-table attributions (forest_shap,
@@ -4274,6 +4467,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("splits"), py::arg("medians"), py::arg("cls_kind"),
         py::arg("n_trees"), py::arg("block_target") = 2048);
   m.attr("ISHAP_MAX_BACKGROUND") = py::int_(ISHAP_MAX_BACKGROUND);
+  m.def("forest_whatif", &forest_whatif,
+        "What-if raw forest sums f64[J,R]: every sample row under every "
+        "job's one or two column overrides (partial dependence; gfx950)",
+        py::arg("codes"), py::arg("nums"), py::arg("cls_nodes"),
+        py::arg("cls_off"), py::arg("feat_col"), py::arg("feat_code"),
+        py::arg("medians"), py::arg("jobs"), py::arg("block_target") = 8192);
+  m.attr("WHATIF_ROWS_PER_BLOCK") = py::int_(WHATIF_BLOCK);
   m.def("hgbt_hist", &hgbt_hist,
         "HistGBT level histogram i64[n_nodes,3,total_bins] of int32 "
         "fixed-point gradients (gfx950)",
