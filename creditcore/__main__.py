@@ -8,6 +8,7 @@ Replaces the reference's Databricks bundle + GitHub Actions + Bicep pipeline
     python -m creditcore serve  [--model-directory ./model] [--port 5000] ...
     python -m creditcore smoke  [--url http://127.0.0.1:5000]
     python -m creditcore pdp    --model-directory ./model --features credit_limit,age --out pdp.json
+    python -m creditcore counterfactual --model-directory ./model --data rows.csv --out cf.json
 """
 
 from __future__ import annotations
@@ -291,6 +292,41 @@ def _cmd_pdp(argv):
                       "sample_rows": doc["sample_rows"], "device": eng.device}))
 
 
+def _cmd_counterfactual(argv):
+    """Offline single-feature counterfactuals of CSV rows under a packaged
+    model, written as JSON (ScoringEngine.counterfactuals)."""
+    p = argparse.ArgumentParser(prog="creditcore counterfactual")
+    p.add_argument("--model-directory", default="./model")
+    p.add_argument("--data", required=True,
+                   help="CSV rows (the train --data schema); at most 1024 rows")
+    p.add_argument("--features", default=None,
+                   help="comma-separated feature names (default: all)")
+    p.add_argument("--threshold", type=float, default=0.5)
+    p.add_argument("--curves", action="store_true",
+                   help="also write the exact curve of every numeric feature")
+    p.add_argument("--device", default="auto")
+    p.add_argument("--out", required=True)
+    a = p.parse_args(argv)
+    import pandas as pd
+
+    from .engine import load_engine
+
+    eng = load_engine(a.model_directory, device=a.device)
+    features = [n.strip() for n in a.features.split(",")] if a.features else None
+    doc = eng.counterfactual_records(
+        pd.read_csv(a.data), features=features, threshold=a.threshold, curves=a.curves
+    )
+    for row in doc["rows"]:
+        for entry in row["counterfactuals"].values():
+            for key in ("thresholds", "probabilities"):
+                if key in entry:
+                    entry[key] = entry[key].tolist()
+    with open(a.out, "w") as f:
+        json.dump(doc, f)
+    print(json.dumps({"out": a.out, "rows": len(doc["rows"]),
+                      "features": len(doc["features"]), "device": eng.device}))
+
+
 def _cmd_generate_data(argv):
     """Write a UCI-shaped synthetic CSV (the reference's curated.csv analog,
     reference databricks/data/; the real UCI CSV is not available offline)."""
@@ -326,6 +362,7 @@ def main():
         "score-batch": _cmd_score_batch,
         "generate-data": _cmd_generate_data,
         "pdp": _cmd_pdp,
+        "counterfactual": _cmd_counterfactual,
     }
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         print(f"usage: python -m creditcore {{{'|'.join(cmds)}}} [args]", file=sys.stderr)

@@ -178,6 +178,17 @@ class ScoringEngine:
     # profiles/bench_results/pdp_micro.txt. The largest call the caps allow
     # (10.7 M pairs) runs as six launches.
     PDP_LAUNCH_PAIRS = 2097152
+    # counterfactuals: most {row, numeric column} jobs of one forest_sweep
+    # launch; a call above it runs as several launches over job slices. Held
+    # against the method="shap" launch at SHAP_MAX_ROWS measured in the same
+    # run, which a sweep launch may not exceed: forest_shap at 1024 rows
+    # 60.35 ms, forest_sweep at 4096 jobs 16.28 ms on an MI355X with the
+    # flagship forest (RF 500 x depth 16, 51k-62k thresholds per column;
+    # bench/cf_micro.py, profiles/bench_results/cf_micro.txt). A launch holds
+    # its jobs' curves on the device (8 B per interval: 1.7 GB at that
+    # shape). The largest call the caps allow (1024 rows x 14 columns =
+    # 14,336 jobs) runs as four launches.
+    CF_LAUNCH_JOBS = 4096
 
     def __init__(
         self,
@@ -203,6 +214,9 @@ class ScoringEngine:
         self._ishap = None
         self._ishap_dev = None
         self._pdp_sample_dev = None  # partial_dependence: the packed sample
+        # counterfactuals: lazily derived breakpoint tables, their device copy
+        self._cf = None
+        self._cf_dev = None
         if device == "cuda":
             self._init_gpu()
 
@@ -803,6 +817,203 @@ class ScoringEngine:
                 return out.cpu().numpy()  # D2H copy synchronizes the stream
 
         return run
+
+    # ---------------------------------------------------- counterfactuals
+    def counterfactuals(
+        self,
+        codes: np.ndarray,
+        nums: np.ndarray,
+        features=None,
+        threshold: float = 0.5,
+        curves: bool = False,
+    ) -> dict:
+        """The smallest change to ONE feature that flips the classifier's
+        decision ``probability > threshold`` of each row, every other feature
+        held fixed. Exact with respect to the packed f32 thresholds: for a
+        numeric feature the model output is piecewise constant, its
+        breakpoints are the thresholds the forest tests on the column
+        (creditcore/counterfactual.py), and the whole curve over those K + 1
+        intervals is computed (forest_sweep_kernel; cpu_ref.forest_sweep_cpu
+        with device="cpu") and searched for the nearest flip on each side. A
+        categorical feature is tried code by code over its vocabulary through
+        the what-if kernel of partial_dependence.
+
+        ``features`` defaults to all 23 names. Returns ``{"threshold",
+        "features", "rows"}``; a row holds ``probability``, ``decision`` (0/1)
+        and ``counterfactuals``, one entry per feature. Numeric: ``value``
+        (the imputed own value), ``below`` / ``above``, each None or
+        ``{value, delta, probability}`` with ``value`` the closest f32 whose
+        decision differs (above: the next f32 after the flipping interval's
+        lower threshold; below: its upper threshold). With ``curves=True``
+        also ``thresholds`` (K) and ``probabilities`` (K + 1). Categorical:
+        ``value`` (the own category, None if unknown) and ``flips``, the
+        ``{category, probability}`` of every other known category whose
+        decision differs, in vocabulary order. The decision is taken in raw
+        space (``raw > cut``, counterfactual.raw_cut). The scoring session is
+        not touched. Caps (creditcore/counterfactual.py) raise
+        ExplainTooLarge."""
+        from . import counterfactual as cf
+        from . import pdp
+
+        p = self.packed
+        names = cf.parse_features(features)
+        thr = cf.check_threshold(threshold)
+        codes = np.ascontiguousarray(codes, dtype=np.int16)
+        nums = np.ascontiguousarray(nums, dtype=np.float32)
+        r = len(codes)
+        if codes.shape != (r, N_CAT) or nums.shape != (r, N_NUM):
+            raise ValueError(f"rows must be (codes [R, {N_CAT}], nums [R, {N_NUM}])")
+        if r < 1:
+            raise ValueError("counterfactuals needs at least one row")
+        if r > cf.CF_MAX_ROWS:
+            raise ExplainTooLarge(
+                f"counterfactuals is capped at {cf.CF_MAX_ROWS} rows per call (got {r})"
+            )
+        players = [FEATURES.index(n) for n in names]
+        num_cols = [pl - N_CAT for pl in players if pl >= N_CAT]
+        cat_players = [pl for pl in players if pl < N_CAT]
+        cls_kind = int(getattr(p, "cls_kind", 0))
+        cut = cf.raw_cut(p, thr)
+        nums_imp = cpu_ref.impute_nums(p, nums)
+        # the row's own raw sum is entry k0 of any of its curves: a call
+        # without a numeric feature sweeps column 0 for it
+        sweep_cols = num_cols or [0]
+        jobs = cf.sweep_jobs(r, sweep_cols)
+        step = max(1, int(self.CF_LAUNCH_JOBS))
+        with self._explain_lock:
+            tables = self._cf_tables()
+            if curves:
+                points = r * sum(len(tables.thresholds[c]) + 1 for c in num_cols)
+                if points > cf.CF_MAX_CURVE_POINTS:
+                    raise ExplainTooLarge(
+                        f"curves=True would return {points} curve points; the cap is "
+                        f"{cf.CF_MAX_CURVE_POINTS} per call (fewer rows or features)"
+                    )
+            want = bool(curves and num_cols)
+            if self.device == "cuda":
+                cf.check_depth(tables)
+                sweep = self._sweep_gpu(codes, nums, cut, want)
+                whatif = self._whatif_gpu(codes, nums, False) if cat_players else None
+            else:
+                def sweep(jb):
+                    rec, raw, cv = cpu_ref.forest_sweep_cpu(p, codes, nums_imp, jb, cut, tables)
+                    return rec, raw, cv if want else None
+
+                def whatif(jb):
+                    return cpu_ref.forest_whatif_cpu(p, codes, nums_imp, jb)
+            parts = [sweep(jobs[s : s + step]) for s in range(0, len(jobs), step)]
+            rec = np.concatenate([a for a, _, _ in parts]).reshape(r, len(sweep_cols), 3)
+            raw = np.concatenate([b for _, b, _ in parts]).reshape(r, len(sweep_cols), 3)
+            curve_of = [c for _, _, cv in parts for c in cv] if want else None
+            cat_raw = None
+            if cat_players:
+                wj = cf.category_jobs(p.vocabs, cat_players)
+                if len(wj):
+                    wstep = max(1, int(self.PDP_LAUNCH_PAIRS) // r)
+                    cat_raw = np.concatenate(
+                        [whatif(wj[s : s + wstep]) for s in range(0, len(wj), wstep)]
+                    )  # [G, R]
+
+        def prob(x):
+            return pdp.finalize(
+                np.asarray(x, dtype=np.float64), cls_kind, float(p.cls_bias),
+                int(p.cls_n_trees), "probability",
+            )
+
+        own_raw = raw[:, 0, 0]
+        own_dec = own_raw > cut
+        own_prob = prob(own_raw)
+        side_prob = prob(raw)
+        cat_prob = prob(cat_raw) if cat_raw is not None else None
+        cat_at = {}
+        at = 0
+        for pl in cat_players:
+            cat_at[pl] = at
+            at += len(p.vocabs[pl])
+        rows = []
+        for i in range(r):
+            entries = {}
+            for name, pl in zip(names, players):
+                if pl < N_CAT:
+                    vocab = p.vocabs[pl]
+                    own = int(codes[i, pl])
+                    flips = []
+                    for code in range(len(vocab)):
+                        g = cat_at[pl] + code
+                        if code != own and bool(cat_raw[g, i] > cut) != bool(own_dec[i]):
+                            flips.append(
+                                {"category": vocab[code], "probability": float(cat_prob[g, i])}
+                            )
+                    entries[name] = {
+                        "value": vocab[own] if 0 <= own < len(vocab) else None,
+                        "flips": flips,
+                    }
+                    continue
+                c = pl - N_CAT
+                s = num_cols.index(c)
+                t = tables.thresholds[c]
+                own = float(nums_imp[i, c])
+                _, kb, ka = (int(k) for k in rec[i, s])
+                entry = {
+                    "value": own,
+                    "below": cf.side_entry(t, kb, False, own, side_prob[i, s, 1]) if kb >= 0 else None,
+                    "above": cf.side_entry(t, ka, True, own, side_prob[i, s, 2]) if ka >= 0 else None,
+                }
+                if curves:
+                    entry["thresholds"] = t.astype(np.float64)
+                    entry["probabilities"] = prob(curve_of[i * len(num_cols) + s])
+                entries[name] = entry
+            rows.append(
+                {
+                    "probability": float(own_prob[i]),
+                    "decision": int(own_dec[i]),
+                    "counterfactuals": entries,
+                }
+            )
+        return {"threshold": thr, "features": names, "rows": rows}
+
+    def _cf_tables(self):
+        """The breakpoint tables of counterfactuals, derived once from the
+        packed forest; the caller holds _explain_lock."""
+        from . import counterfactual as cf
+
+        if self._cf is None:
+            _check_forest_tables(self.packed)
+            self._cf = cf.build_tables(self.packed)
+        return self._cf
+
+    def _sweep_gpu(self, codes: np.ndarray, nums: np.ndarray, cut: float, want_curves: bool):
+        """One-launch runner of forest_sweep on the device ({row, column} job
+        table in; records, raw sums and, when asked, curves out); the caller
+        holds _explain_lock. Breakpoint tables are uploaded once, next to
+        the forest tables of _forest_dev."""
+        import torch
+
+        from .ops import gpu
+
+        dev = torch.device("cuda", self.device_index)
+        m = self._forest_dev()
+        t = self._cf_tables()
+        if self._cf_dev is None:
+            self._cf_dev = {
+                "node_rank": torch.from_numpy(t.node_rank).to(dev),
+                "thr": torch.from_numpy(t.thr).to(dev),
+                "thr_off": torch.from_numpy(t.thr_off),  # host: the binding checks it
+                "max_depth": t.max_depth,
+            }
+        sw = self._cf_dev
+        rows = (torch.from_numpy(codes).to(dev), torch.from_numpy(nums).to(dev))
+
+        def run(jb: np.ndarray):
+            with torch.cuda.device(dev):
+                return gpu.forest_sweep(rows[0], rows[1], m, sw, jb, cut, want_curves)
+
+        return run
+
+    def counterfactual_records(self, records, **kw) -> dict:
+        """counterfactuals on a request body (list of dicts / DataFrame)."""
+        codes, nums = encode_batch(records, self.packed.vocabs)
+        return self.counterfactuals(codes, nums, **kw)
 
     def explain_records(
         self,

@@ -156,6 +156,64 @@ def forest_whatif_cpu(
     return out
 
 
+def forest_sweep_cpu(
+    packed: PackedModel,
+    codes: np.ndarray,
+    nums_imp: np.ndarray,
+    jobs: np.ndarray,
+    cut: float | None = None,
+    tables=None,
+):
+    """Exact single-feature curves and their nearest decision flips, the
+    reference of forest_sweep_kernel. ``jobs`` is i32[J, 2] {row, numeric
+    column}; ``cut`` the decision threshold in raw space (class 1 is
+    ``raw > cut``; default: counterfactual.raw_cut at 0.5).
+
+    Returns ``(rec, raw, curves)``: rec i32[J, 3] = {k0, k_below, k_above}
+    (-1 = none), raw f64[J, 3] the raw sums there (0.0 where none) and curves,
+    a list of J arrays f64[K + 1]. Deliberately the dumb version: the row is
+    scored by forest_whatif_cpu at one representative value per interval (the
+    threshold T[k] for k < K, the next f32 above T[K-1] for the last) and the
+    curve is searched with plain numpy. It shares no code with the kernel's
+    interval walk; only the threshold lists come from the same tables."""
+    from .. import counterfactual as cf
+
+    jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, 2)
+    codes = np.ascontiguousarray(codes, dtype=np.int16)
+    nums_imp = np.ascontiguousarray(nums_imp, dtype=np.float32)
+    n_jobs, r = len(jobs), len(codes)
+    if n_jobs < 1 or r < 1:
+        raise ValueError("forest_sweep needs at least one job and one row")
+    if ((jobs[:, 0] < 0) | (jobs[:, 0] >= r) | (jobs[:, 1] < 0) | (jobs[:, 1] >= N_NUM)).any():
+        raise ValueError("job rows and numeric columns must be in range")
+    if tables is None:
+        tables = cf.build_tables(packed)
+    if cut is None:
+        cut = cf.raw_cut(packed, 0.5)
+    rec = np.full((n_jobs, 3), -1, dtype=np.int32)
+    raw = np.zeros((n_jobs, 3), dtype=np.float64)
+    curves: list = [None] * n_jobs
+    for c in np.unique(jobs[:, 1]):
+        mine = np.flatnonzero(jobs[:, 1] == c)
+        rows, slot = np.unique(jobs[mine, 0], return_inverse=True)
+        thr = tables.thresholds[c]
+        values = cf.representatives(thr)
+        wj = np.zeros((len(values), 4), dtype=np.int32)
+        wj[:, 0], wj[:, 1], wj[:, 2] = N_CAT + c, values.view(np.int32), -1
+        sums = forest_whatif_cpu(packed, codes[rows], nums_imp[rows], wj)  # [K+1, rows]
+        for j, s in zip(mine, slot):
+            curve = np.ascontiguousarray(sums[:, s])
+            k0 = int(np.sum(thr < nums_imp[jobs[j, 0], c]))
+            flips = np.flatnonzero((curve > cut) != (curve[k0] > cut))
+            below, above = flips[flips < k0], flips[flips > k0]
+            kb = int(below[-1]) if len(below) else -1
+            ka = int(above[0]) if len(above) else -1
+            rec[j] = (k0, kb, ka)
+            raw[j] = (curve[k0], curve[kb] if kb >= 0 else 0.0, curve[ka] if ka >= 0 else 0.0)
+            curves[j] = curve
+    return rec, raw, curves
+
+
 def forest_contrib_cpu(
     packed: PackedModel, codes: np.ndarray, nums_imp: np.ndarray
 ) -> np.ndarray:

@@ -121,13 +121,14 @@ def _pack_tree_arrays(
         else:
             f = int(feat[i])
             nodes[k, 0] = f if feature_remap is None else int(feature_remap[f])
-            # sklearn predict casts X to float32 but keeps float64 thresholds;
-            # ceil the threshold to the next float32 so that
-            # {f32(x) <= thr32} == {f32(x) <= thr64} for every float32 x
-            # (no float32 value lies in (thr64, ceil32(thr64))).
+            # sklearn predict casts X to float32 but keeps float64 thresholds
+            # and compares in double; floor the threshold to float32 so that
+            # {f32(x) <= thr32} == {f32(x) <= thr64} for every float32 x (no
+            # float32 value lies in (floor32(thr64), thr64]; rounding up
+            # would send x == ceil32(thr64) left where sklearn sends it right).
             t32 = np.float32(thr[i])
-            if np.float64(t32) < thr[i]:
-                t32 = np.nextafter(t32, np.float32(np.inf), dtype=np.float32)
+            if np.float64(t32) > thr[i]:
+                t32 = np.nextafter(t32, np.float32(-np.inf), dtype=np.float32)
             f32[k] = t32
             nodes[k, 2] = int(new_idx[cl[i]])
             nodes[k, 3] = int(new_idx[cr[i]])

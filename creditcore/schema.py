@@ -194,6 +194,66 @@ class PdpOutput(BaseModel):
     results: list[PdpCurve]
 
 
+class CounterfactualRequest(BaseModel):
+    """POST /explain/counterfactual request: the records as /explain takes
+    them, the features to move (default: all), the decision threshold on the
+    predicted probability and whether to return the whole exact curves."""
+
+    records: list[dict]
+    features: list[str] | None = None
+    threshold: float = 0.5
+    curves: bool = False
+
+    model_config = ConfigDict(extra="ignore")
+
+
+class CounterfactualSide(BaseModel):
+    """The closest value on one side of a numeric feature whose decision
+    differs from the row's own."""
+
+    value: float
+    delta: float
+    probability: float
+
+
+class NumericCounterfactual(BaseModel):
+    """``value`` is the row's own (imputed) value; ``thresholds`` (K) and
+    ``probabilities`` (K + 1, one per interval) only with ``curves``."""
+
+    value: float
+    below: CounterfactualSide | None = None
+    above: CounterfactualSide | None = None
+    thresholds: list[float] | None = None
+    probabilities: list[float] | None = None
+
+
+class CategoryFlip(BaseModel):
+    category: str
+    probability: float
+
+
+class CategoricalCounterfactual(BaseModel):
+    """``value`` is the row's own category (null if unknown); ``flips`` the
+    other known categories whose decision differs, in vocabulary order."""
+
+    value: str | None = None
+    flips: list[CategoryFlip]
+
+
+class CounterfactualRow(BaseModel):
+    probability: float
+    decision: int
+    counterfactuals: dict[str, NumericCounterfactual | CategoricalCounterfactual]
+
+
+class CounterfactualOutput(BaseModel):
+    """POST /explain/counterfactual response: one entry per record."""
+
+    threshold: float
+    features: list[str]
+    rows: list[CounterfactualRow]
+
+
 # The one-record CI smoke-test fixture (reference app/sample-request.json).
 SAMPLE_REQUEST: list[dict] = [
     {

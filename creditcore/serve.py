@@ -38,6 +38,8 @@ from .engine import (
 from .pack import encode_batch
 from .schema import (
     FEATURES,
+    CounterfactualOutput,
+    CounterfactualRequest,
     ExplainOutput,
     LoanApplicant,
     ModelOutput,
@@ -704,6 +706,63 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
         }
         metrics.observe_request(int(out["sample_rows"]), (time.perf_counter() - t0) * 1e3)
         return _json_response(payload)
+
+    @app.post("/explain/counterfactual", response_model=CounterfactualOutput)
+    async def explain_counterfactual(req: CounterfactualRequest):
+        """Single-feature counterfactuals of the classifier for the posted
+        records: per record and feature, the closest value on each side whose
+        decision ``probability > threshold`` differs, exact with respect to
+        the packed thresholds (``curves=true`` adds the whole piecewise
+        constant curve). One attempt on one live replica; bypasses the
+        micro-batcher."""
+        import asyncio
+
+        from .counterfactual import CF_MAX_ROWS
+
+        metrics: Metrics = state["metrics"]
+        engines = state["engines"]
+        pool: ReplicaPool = state["pool"]
+        if not req.records:
+            raise HTTPException(status_code=400, detail="empty request batch")
+        if len(req.records) > CF_MAX_ROWS:
+            raise HTTPException(
+                status_code=413,
+                detail=f"/explain/counterfactual takes at most {CF_MAX_ROWS} rows",
+            )
+        try:
+            codes, nums = encode_batch(req.records, engines[0].packed.vocabs)
+        except (ValueError, TypeError, KeyError) as e:
+            raise HTTPException(status_code=422, detail=f"bad record: {e}")
+        try:
+            idx = pool.pick()
+        except RuntimeError:
+            metrics.observe_error()
+            raise HTTPException(status_code=503, detail="no healthy replicas")
+        t0 = time.perf_counter()
+
+        def call():
+            return engines[idx].counterfactuals(
+                codes, nums, features=req.features, threshold=req.threshold, curves=req.curves
+            )
+
+        try:
+            out = await asyncio.get_running_loop().run_in_executor(None, call)
+            pool.report_ok(idx)
+        except ExplainTooLarge as e:  # the request's fault, not the replica's
+            raise HTTPException(status_code=413, detail=str(e))
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        except Exception as e:
+            metrics.observe_error()
+            pool.report_fail(idx)
+            raise HTTPException(status_code=500, detail=f"counterfactuals failed: {e}")
+        for row in out["rows"]:
+            for entry in row["counterfactuals"].values():
+                for key in ("thresholds", "probabilities"):
+                    if key in entry:
+                        entry[key] = entry[key].tolist()
+        metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
+        return _json_response(out)
 
     @app.get("/healthz")
     async def healthz(deep: bool = False):

@@ -1036,6 +1036,269 @@ __global__ __launch_bounds__(WHATIF_BLOCK) void forest_whatif_kernel(
   }
 }
 
+// Exact single-feature sweep for counterfactuals: the raw classifier sum of
+// one row as ONE numeric column moves over the whole real line, every other
+// column held fixed. The sum is piecewise constant in that column; its
+// breakpoints are the K distinct f32 thresholds the forest tests on it
+// (creditcore/counterfactual.py builds them, sorted, with the rank of every
+// node's threshold in node_rank). Interval k is (T[k-1], T[k]], K+1 in all.
+//
+// A job is {row, numeric column}. A tree is walked ONCE per job and chunk of
+// the curve, depth first, left child first, carrying the rank range [lo, hi)
+// that reaches the node: a node on another column (or a one-hot node) is
+// decided by the row, a node of rank r on the swept column sends
+// [lo, min(hi, r+1)) left and [max(lo, r+1), hi) right, and an empty half is
+// not descended. Left first means the leaves come out in ascending rank order
+// and tile the range, so a tree's answer is a short list {end, leaf}: segment
+// s covers [end[s-1], end[s]). The stack holds {right child, hi} of the nodes
+// whose both halves are alive; the range's lo is the end of the last segment.
+//
+// One block of SWEEP_BLOCK threads per (job, chunk of SWEEP_CHUNK intervals).
+// Phase A: thread u walks tree b0+u (a batch of SWEEP_BLOCK trees) restricted
+// to the chunk's range and leaves its segment list in LDS (SWEEP_SEG_CAP
+// segments; a path tests one column only a few times). Phase B: every thread
+// owns SWEEP_IPT consecutive intervals in registers and goes through the
+// batch IN TREE ORDER, adding the leaf of the segment each interval falls
+// in (broadcast LDS reads). A tree with more segments than the list holds is
+// re-walked in phase B by each thread over its own few intervals: slower,
+// still exact, still in tree order. So every interval's f64 sum is the
+// tree-order sum forest_whatif_kernel computes for a value inside it: plain
+// stores, no atomics, bit-identical to the reference.
+//
+// Bounds by construction: node indices are compared unsigned against the
+// tree's node count before every load, the walk loop runs at most that many
+// times (a depth-first walk sees a node once), the stack push is guarded by
+// SWEEP_MAX_DEPTH (the host refuses deeper forests before any launch),
+// source columns are clamped and curve stores are guarded by the chunk's end.
+#define SWEEP_BLOCK 256
+#define SWEEP_IPT 4
+#define SWEEP_CHUNK (SWEEP_BLOCK * SWEEP_IPT)
+#define SWEEP_SEG_CAP 8
+#define SWEEP_MAX_DEPTH 64
+
+template <class Emit>
+__device__ __forceinline__ void sweep_walk_tree(
+    const int4* __restrict__ nodes, const int* __restrict__ node_rank,
+    int base, unsigned n_tree_nodes,
+    const int* __restrict__ feat_col, const int* __restrict__ feat_code, unsigned n_feat,
+    const short* s_codes, const float* s_nums,
+    int col, int lo, int hi, Emit&& emit)
+{
+  int stk_node[SWEEP_MAX_DEPTH];
+  int stk_hi[SWEEP_MAX_DEPTH];
+  int sp = 0;
+  unsigned rel = 0;
+  for (unsigned it = 0; it < n_tree_nodes; ++it) {
+    if (rel >= n_tree_nodes) return;
+    const int4 nd = nodes[base + rel];
+    if ((unsigned)nd.x >= n_feat) {  // a leaf (feat = -1)
+      emit(hi, __int_as_float(nd.y));
+      if (sp == 0) return;
+      --sp;
+      lo = hi;
+      rel = (unsigned)stk_node[sp];
+      hi = stk_hi[sp];
+      continue;
+    }
+    const int fcol = feat_col[nd.x];
+    const int code = feat_code[nd.x];
+    if (code < 0 && fcol == col) {
+      const int mid = node_rank[base + rel] + 1;  // ranks <= r go left
+      if (mid >= hi) {
+        rel = (unsigned)nd.z;
+      } else if (mid <= lo) {
+        rel = (unsigned)nd.w;
+      } else {
+        if ((unsigned)sp < (unsigned)SWEEP_MAX_DEPTH) {
+          stk_node[sp] = nd.w;
+          stk_hi[sp] = hi;
+          ++sp;
+        }
+        hi = mid;
+        rel = (unsigned)nd.z;
+      }
+    } else {
+      const float v =
+          (code >= 0) ? ((s_codes[min((unsigned)fcol, (unsigned)(N_CAT - 1))] == (short)code) ? 1.0f : 0.0f)
+                      : s_nums[min((unsigned)fcol, (unsigned)(N_NUM - 1))];
+      rel = (unsigned)((v <= __int_as_float(nd.y)) ? nd.z : nd.w);
+    }
+  }
+}
+
+__global__ __launch_bounds__(SWEEP_BLOCK) void forest_sweep_kernel(
+    const short* __restrict__ codes,     // [R, N_CAT]
+    const float* __restrict__ nums,      // [R, N_NUM], NaNs not yet imputed
+    const float* __restrict__ medians,   // [N_NUM]
+    const int4* __restrict__ nodes,      // [n_nodes] {feat, bits, left, right}
+    const int* __restrict__ node_rank,   // [n_nodes] threshold rank, -1 = none
+    const int* __restrict__ tree_off,    // [T+1]
+    int n_trees,
+    unsigned n_nodes,
+    const int* __restrict__ feat_col,    // [F]
+    const int* __restrict__ feat_code,   // [F]
+    unsigned n_feat,
+    const int* __restrict__ thr_off,     // [N_NUM+1] offsets of the threshold lists
+    const int2* __restrict__ jobs,       // [J] {row, numeric column}
+    const long long* __restrict__ curve_off,  // [J] first curve entry of the job
+    int n_jobs,
+    int n_rows,
+    double* __restrict__ curves)         // ragged: K+1 sums per job, all written
+{
+  __shared__ short s_codes[N_CAT];
+  __shared__ float s_nums[N_NUM];
+  __shared__ int s_end[SWEEP_SEG_CAP * SWEEP_BLOCK];
+  __shared__ float s_val[SWEEP_SEG_CAP * SWEEP_BLOCK];
+  __shared__ int s_nseg[SWEEP_BLOCK];
+
+  const int tid = threadIdx.x;
+  const int j = blockIdx.x;
+  if (j >= n_jobs) return;
+  const int2 job = jobs[j];
+  const int row = job.x, col = job.y;
+  if ((unsigned)row >= (unsigned)n_rows || (unsigned)col >= (unsigned)N_NUM) return;
+  const int n_int = thr_off[col + 1] - thr_off[col] + 1;  // K + 1 intervals
+  const long long c0l = (long long)blockIdx.y * SWEEP_CHUNK;
+  if (c0l >= n_int) return;  // the grid is sized for the longest curve
+  const int c0 = (int)c0l;
+  const int c1 = min(c0 + SWEEP_CHUNK, n_int);
+
+  // the job's row, imputed exactly as forest_whatif_kernel stages its rows
+  if (tid < N_CAT) s_codes[tid] = codes[(size_t)row * N_CAT + tid];
+  if (tid >= 32 && tid < 32 + N_NUM) {
+    const float v = nums[(size_t)row * N_NUM + (tid - 32)];
+    s_nums[tid - 32] = isnan(v) ? medians[tid - 32] : v;
+  }
+  __syncthreads();
+
+  const int kb = c0 + tid * SWEEP_IPT;  // the thread's own intervals
+  double acc[SWEEP_IPT];
+#pragma unroll
+  for (int i = 0; i < SWEEP_IPT; ++i) acc[i] = 0.0;
+
+  for (int b0 = 0; b0 < n_trees; b0 += SWEEP_BLOCK) {
+    // phase A: one tree per thread, its segment list into LDS
+    const int t = b0 + tid;
+    if (t < n_trees) {
+      const int base = tree_off[t];
+      const int size = tree_off[t + 1] - base;
+      int n = 0;
+      if (base >= 0 && size > 0 && (unsigned)base + (unsigned)size <= n_nodes) {
+        sweep_walk_tree(nodes, node_rank, base, (unsigned)size, feat_col, feat_code, n_feat,
+                        s_codes, s_nums, col, c0, c1, [&](int end, float v) {
+                          if (n < SWEEP_SEG_CAP) {
+                            s_end[n * SWEEP_BLOCK + tid] = end;
+                            s_val[n * SWEEP_BLOCK + tid] = v;
+                          }
+                          ++n;
+                        });
+      }
+      s_nseg[tid] = min(n, SWEEP_SEG_CAP + 1);
+    }
+    __syncthreads();
+
+    // phase B: the batch in tree order
+    const int nb = min(SWEEP_BLOCK, n_trees - b0);
+    for (int u = 0; u < nb; ++u) {
+      const int n = s_nseg[u];
+      if (n == 1) {  // the tree does not see the column on this row's path
+        const double v = (double)s_val[u];
+#pragma unroll
+        for (int i = 0; i < SWEEP_IPT; ++i) acc[i] += v;
+      } else if (n <= SWEEP_SEG_CAP) {
+        if (n > 0) {
+#pragma unroll
+          for (int i = 0; i < SWEEP_IPT; ++i) {
+            int s = 0;
+            while (s + 1 < n && kb + i >= s_end[s * SWEEP_BLOCK + u]) ++s;
+            acc[i] += (double)s_val[s * SWEEP_BLOCK + u];
+          }
+        }
+      } else if (kb < c1) {  // list overflow: walk the tree over the own intervals
+        const int base = tree_off[b0 + u];
+        const int size = tree_off[b0 + u + 1] - base;  // checked in phase A (n > 0)
+        int cur = kb;
+        sweep_walk_tree(nodes, node_rank, base, (unsigned)size, feat_col, feat_code, n_feat,
+                        s_codes, s_nums, col, kb, min(kb + SWEEP_IPT, c1),
+                        [&](int end, float v) {
+#pragma unroll
+                          for (int i = 0; i < SWEEP_IPT; ++i)
+                            if (kb + i >= cur && kb + i < end) acc[i] += (double)v;
+                          cur = end;
+                        });
+      }
+    }
+    __syncthreads();  // the lists are rewritten by the next batch
+  }
+
+  double* out = curves + curve_off[j];
+#pragma unroll
+  for (int i = 0; i < SWEEP_IPT; ++i)
+    if (kb + i < c1) out[kb + i] = acc[i];
+}
+
+// Search phase of the sweep: per job the row's own interval k0 (the number of
+// thresholds below its imputed value) and the nearest interval on each side
+// whose decision `raw > cut` differs from the decision at k0. One block per
+// job strides over the curve; the two nearest indices are reduced with
+// integer LDS atomics (order-free). Record {k0, k_below, k_above}, -1 = none,
+// and the three raw sums (0.0 where there is none).
+__global__ __launch_bounds__(SWEEP_BLOCK) void forest_sweep_search_kernel(
+    const float* __restrict__ nums,      // [R, N_NUM]
+    const float* __restrict__ medians,   // [N_NUM]
+    const float* __restrict__ thr,       // thresholds of all columns, sorted per column
+    const int* __restrict__ thr_off,     // [N_NUM+1]
+    const int2* __restrict__ jobs,       // [J]
+    const long long* __restrict__ curve_off,  // [J]
+    const double* __restrict__ curves,
+    double cut,
+    int n_jobs,
+    int n_rows,
+    int* __restrict__ rec,               // [J, 3]
+    double* __restrict__ raw)            // [J, 3]
+{
+  __shared__ int s_below, s_above;
+  const int tid = threadIdx.x;
+  const int j = blockIdx.x;
+  if (j >= n_jobs) return;
+  const int2 job = jobs[j];
+  const int row = job.x, col = job.y;
+  if ((unsigned)row >= (unsigned)n_rows || (unsigned)col >= (unsigned)N_NUM) return;
+  const int t0 = thr_off[col];
+  const int K = thr_off[col + 1] - t0;
+  float v = nums[(size_t)row * N_NUM + col];
+  if (isnan(v)) v = medians[col];
+  int a = 0, b = K;  // lower bound: the number of thresholds < v
+  while (a < b) {
+    const int m = (a + b) >> 1;
+    if (thr[t0 + m] < v) a = m + 1; else b = m;
+  }
+  const int k0 = a;  // 0..K
+  const double* c = curves + curve_off[j];
+  const bool d0 = c[k0] > cut;
+  if (tid == 0) { s_below = -1; s_above = K + 1; }
+  __syncthreads();
+  int below = -1, above = K + 1;
+  for (int k = tid; k <= K; k += SWEEP_BLOCK) {
+    if ((c[k] > cut) != d0) {
+      if (k < k0) below = max(below, k);
+      else above = min(above, k);  // k != k0: the decision at k0 is d0
+    }
+  }
+  if (below >= 0) atomicMax(&s_below, below);
+  if (above <= K) atomicMin(&s_above, above);
+  __syncthreads();
+  if (tid == 0) {
+    const int kb = s_below, ka = (s_above <= K) ? s_above : -1;
+    rec[3 * j] = k0;
+    rec[3 * j + 1] = kb;
+    rec[3 * j + 2] = ka;
+    raw[3 * j] = c[k0];
+    raw[3 * j + 1] = (kb >= 0) ? c[kb] : 0.0;
+    raw[3 * j + 2] = (ka >= 0) ? c[ka] : 0.0;
+  }
+}
+
 // 4-tree ILP + optional transposed grid (blockIdx.x = tree chunk so the
 // dispatcher's id%8 XCD placement gives adjacent chunks to different XCDs,
 // keeping each XCD's L2 on a tree subset). Experimental A/B variants.
@@ -1700,6 +1963,117 @@ torch::Tensor forest_whatif(
       out.data_ptr<double>());
   HIP_CHECK(hipGetLastError());
   return out;
+}
+
+// Exact single-feature sweep (forest_sweep_kernel + forest_sweep_search_kernel)
+// for counterfactuals. `jobs` is a HOST i32[J, 2] table {row, numeric column},
+// `thr_off` a HOST i32[N_NUM+1] table of offsets into `thr` (the sorted
+// distinct thresholds of every numeric column, on the device); both are
+// checked here and copied to the device on the caller's stream. `node_rank`
+// is index-aligned with cls_nodes. `max_depth` is the deepest tree of the
+// forest as the caller measured it (the walk's stack bound). Returns
+// {rec i32[J,3] = {k0, k_below, k_above}, raw f64[J,3], curves}: curves is
+// the ragged f64 buffer (K+1 sums per job, job after job) when `want_curves`
+// and an empty tensor otherwise. The caller has bounds-checked the forest
+// tables (engine._check_forest_tables).
+std::vector<torch::Tensor> forest_sweep(
+    torch::Tensor codes, torch::Tensor nums,
+    torch::Tensor cls_nodes, torch::Tensor cls_off,
+    torch::Tensor feat_col, torch::Tensor feat_code,
+    torch::Tensor medians, torch::Tensor node_rank,
+    torch::Tensor thr, torch::Tensor thr_off, torch::Tensor jobs,
+    double cut, int64_t max_depth, bool want_curves)
+{
+  check_inputs(codes, nums);
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType st, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == codes.device(), name,
+                " must be on the inputs' GPU");
+    TORCH_CHECK(t.scalar_type() == st && t.is_contiguous(), name,
+                " has the wrong dtype or is not contiguous");
+  };
+  on_dev(nums, torch::kFloat32, "nums");
+  on_dev(cls_nodes, torch::kInt32, "cls_nodes");
+  on_dev(cls_off, torch::kInt32, "cls_off");
+  on_dev(feat_col, torch::kInt32, "feat_col");
+  on_dev(feat_code, torch::kInt32, "feat_code");
+  on_dev(medians, torch::kFloat32, "medians");
+  on_dev(node_rank, torch::kInt32, "node_rank");
+  on_dev(thr, torch::kFloat32, "thr");
+  TORCH_CHECK(cls_nodes.dim() == 2 && cls_nodes.size(1) == 4, "cls_nodes must be [n, 4]");
+  TORCH_CHECK(node_rank.dim() == 1 && node_rank.numel() == cls_nodes.size(0),
+              "node_rank must hold one rank per classifier node");
+  TORCH_CHECK(feat_col.numel() == feat_code.numel(), "feat_col/feat_code size mismatch");
+  TORCH_CHECK(medians.numel() == N_NUM, "medians must have N_NUM entries");
+  TORCH_CHECK(cls_off.numel() >= 2, "forest has no trees");
+  TORCH_CHECK(cls_nodes.size(0) < (int64_t(1) << 31), "too many nodes");
+  TORCH_CHECK(max_depth >= 0 && max_depth <= SWEEP_MAX_DEPTH,
+              "forest depth ", max_depth, " exceeds the sweep's stack bound ", SWEEP_MAX_DEPTH);
+  TORCH_CHECK(std::isfinite(cut), "cut must be finite");
+  TORCH_CHECK(!thr_off.is_cuda() && thr_off.scalar_type() == torch::kInt32 &&
+              thr_off.is_contiguous() && thr_off.dim() == 1 && thr_off.numel() == N_NUM + 1,
+              "thr_off must be a contiguous host int32 [N_NUM+1] table");
+  TORCH_CHECK(!jobs.is_cuda() && jobs.scalar_type() == torch::kInt32 &&
+              jobs.is_contiguous() && jobs.dim() == 2 && jobs.size(1) == 2,
+              "jobs must be a contiguous host int32 [J, 2] table");
+  const int* to = thr_off.data_ptr<int>();
+  TORCH_CHECK(to[0] == 0 && (int64_t)to[N_NUM] == thr.numel(), "thr_off does not span thr");
+  for (int c = 0; c < N_NUM; ++c)
+    TORCH_CHECK(to[c + 1] >= to[c], "thr_off must not decrease");
+
+  const int64_t J = jobs.size(0);
+  const int64_t R = codes.size(0);
+  TORCH_CHECK(J >= 1, "forest_sweep needs at least one job");
+  TORCH_CHECK(R >= 1, "forest_sweep needs at least one row");
+  TORCH_CHECK(J < (int64_t(1) << 31) && R < (int64_t(1) << 31), "too many jobs or rows");
+  const int* jb = jobs.data_ptr<int>();
+  auto off_host = torch::empty({J}, torch::TensorOptions().dtype(torch::kInt64));
+  int64_t* oh = off_host.data_ptr<int64_t>();
+  int64_t total = 0, longest = 0;
+  for (int64_t j = 0; j < J; ++j) {
+    const int row = jb[2 * j], col = jb[2 * j + 1];
+    TORCH_CHECK(row >= 0 && row < R, "job ", j, ": row out of range");
+    TORCH_CHECK(col >= 0 && col < N_NUM, "job ", j, ": numeric column out of range");
+    const int64_t n_int = (int64_t)(to[col + 1] - to[col]) + 1;
+    oh[j] = total;
+    total += n_int;
+    longest = std::max(longest, n_int);
+  }
+  const int64_t chunks = (longest + SWEEP_CHUNK - 1) / SWEEP_CHUNK;
+  TORCH_CHECK(chunks <= 65535, "a column has too many thresholds for one launch");
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)codes.get_device());
+  auto dev = codes.device();
+  auto curves = torch::empty({total}, torch::TensorOptions().dtype(torch::kFloat64).device(dev));
+  auto rec = torch::empty({J, 3}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
+  auto raw = torch::empty({J, 3}, torch::TensorOptions().dtype(torch::kFloat64).device(dev));
+  auto jobs_dev = jobs.to(dev);
+  auto off_dev = off_host.to(dev);
+  auto thr_off_dev = thr_off.to(dev);
+  // thr may be empty (a forest of leaves): never dereferenced then (K = 0)
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  const int T = (int)cls_off.size(0) - 1;
+  hipLaunchKernelGGL(forest_sweep_kernel, dim3((unsigned)J, (unsigned)chunks),
+      dim3(SWEEP_BLOCK), 0, stream,
+      codes.data_ptr<short>(), nums.data_ptr<float>(), medians.data_ptr<float>(),
+      reinterpret_cast<const int4*>(cls_nodes.data_ptr<int>()), node_rank.data_ptr<int>(),
+      cls_off.data_ptr<int>(), T, (unsigned)cls_nodes.size(0),
+      feat_col.data_ptr<int>(), feat_code.data_ptr<int>(), (unsigned)feat_col.numel(),
+      thr_off_dev.data_ptr<int>(),
+      reinterpret_cast<const int2*>(jobs_dev.data_ptr<int>()),
+      reinterpret_cast<const long long*>(off_dev.data_ptr<int64_t>()), (int)J, (int)R,
+      curves.data_ptr<double>());
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(forest_sweep_search_kernel, dim3((unsigned)J), dim3(SWEEP_BLOCK), 0, stream,
+      nums.data_ptr<float>(), medians.data_ptr<float>(), thr.data_ptr<float>(),
+      thr_off_dev.data_ptr<int>(),
+      reinterpret_cast<const int2*>(jobs_dev.data_ptr<int>()),
+      reinterpret_cast<const long long*>(off_dev.data_ptr<int64_t>()),
+      curves.data_ptr<double>(), cut, (int)J, (int)R,
+      rec.data_ptr<int>(), raw.data_ptr<double>());
+  HIP_CHECK(hipGetLastError());
+  if (!want_curves)
+    curves = torch::empty({0}, torch::TensorOptions().dtype(torch::kFloat64).device(dev));
+  return {rec, raw, curves};
 }
 
 // Host-side checks shared by the path-table attributions (forest_shap,
@@ -4474,6 +4848,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cls_off"), py::arg("feat_col"), py::arg("feat_code"),
         py::arg("medians"), py::arg("jobs"), py::arg("block_target") = 8192);
   m.attr("WHATIF_ROWS_PER_BLOCK") = py::int_(WHATIF_BLOCK);
+  m.def("forest_sweep", &forest_sweep,
+        "Exact single-feature sweep: per {row, numeric column} job the raw "
+        "forest sum of every threshold interval, searched on the device for "
+        "the nearest decision flips (counterfactuals; gfx950)",
+        py::arg("codes"), py::arg("nums"), py::arg("cls_nodes"),
+        py::arg("cls_off"), py::arg("feat_col"), py::arg("feat_code"),
+        py::arg("medians"), py::arg("node_rank"), py::arg("thr"),
+        py::arg("thr_off"), py::arg("jobs"), py::arg("cut"),
+        py::arg("max_depth"), py::arg("want_curves") = false);
+  m.attr("SWEEP_BLOCK") = py::int_(SWEEP_BLOCK);
+  m.attr("SWEEP_CHUNK") = py::int_(SWEEP_CHUNK);
+  m.attr("SWEEP_SEG_CAP") = py::int_(SWEEP_SEG_CAP);
+  m.attr("SWEEP_MAX_DEPTH") = py::int_(SWEEP_MAX_DEPTH);
   m.def("hgbt_hist", &hgbt_hist,
         "HistGBT level histogram i64[n_nodes,3,total_bins] of int32 "
         "fixed-point gradients (gfx950)",
