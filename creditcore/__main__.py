@@ -9,6 +9,7 @@ Replaces the reference's Databricks bundle + GitHub Actions + Bicep pipeline
     python -m creditcore smoke  [--url http://127.0.0.1:5000]
     python -m creditcore pdp    --model-directory ./model --features credit_limit,age --out pdp.json
     python -m creditcore counterfactual --model-directory ./model --data rows.csv --out cf.json
+    python -m creditcore drift-mmd --model-directory ./model --data batch.csv [--reference ref.csv]
 """
 
 from __future__ import annotations
@@ -327,6 +328,38 @@ def _cmd_counterfactual(argv):
                       "features": len(doc["features"]), "device": eng.device}))
 
 
+def _cmd_drift_mmd(argv):
+    """Offline multivariate drift test (MMD with a permutation p-value) of
+    CSV rows under a packaged model (ScoringEngine.mmd_drift)."""
+    p = argparse.ArgumentParser(prog="creditcore drift-mmd")
+    p.add_argument("--model-directory", default="./model")
+    p.add_argument("--data", required=True,
+                   help="CSV batch (the train --data schema); at most 16384 rows")
+    p.add_argument("--reference", default=None,
+                   help="CSV reference sample (default: the model's packed sample)")
+    p.add_argument("--permutations", type=int, default=100)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--device", default="auto")
+    p.add_argument("--out", default=None)
+    a = p.parse_args(argv)
+    import pandas as pd
+
+    from .engine import load_engine
+
+    eng = load_engine(a.model_directory, device=a.device)
+    doc = eng.mmd_drift_records(
+        pd.read_csv(a.data),
+        reference=pd.read_csv(a.reference) if a.reference else None,
+        n_permutations=a.permutations,
+        seed=a.seed,
+    )
+    doc["device"] = eng.device
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(doc, f)
+    print(json.dumps(doc))
+
+
 def _cmd_generate_data(argv):
     """Write a UCI-shaped synthetic CSV (the reference's curated.csv analog,
     reference databricks/data/; the real UCI CSV is not available offline)."""
@@ -363,6 +396,7 @@ def main():
         "generate-data": _cmd_generate_data,
         "pdp": _cmd_pdp,
         "counterfactual": _cmd_counterfactual,
+        "drift-mmd": _cmd_drift_mmd,
     }
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         print(f"usage: python -m creditcore {{{'|'.join(cmds)}}} [args]", file=sys.stderr)

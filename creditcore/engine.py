@@ -189,6 +189,16 @@ class ScoringEngine:
     # shape). The largest call the caps allow (1024 rows x 14 columns =
     # 14,336 jobs) runs as four launches.
     CF_LAUNCH_JOBS = 4096
+    # mmd_drift: most pooled rows i (64-row tiles) of one mmd_perm launch; a
+    # call above it runs as several launches over row slices. Sized like
+    # ISHAP_MAX_PAIRS: the launch at the caps (n = m = 16384, N = 32768
+    # pooled rows, flagship D, P = 100) may take no longer than 1.25 x the
+    # method="shap" launch at SHAP_MAX_ROWS measured in the same run
+    # (bench/mmd_micro.py, profiles/bench_results/mmd_micro.txt): forest_shap
+    # at 1024 rows 60.03 ms (bound 75.04 ms), mmd_perm_w at N = 32768 as one
+    # launch 4.36 ms on an MI355X. The caps allow no larger call, so today no
+    # call is sliced.
+    MMD_LAUNCH_ROWS = 32768
 
     def __init__(
         self,
@@ -217,6 +227,8 @@ class ScoringEngine:
         # counterfactuals: lazily derived breakpoint tables, their device copy
         self._cf = None
         self._cf_dev = None
+        # mmd_drift: (key, mu, sd, z_ref, gamma) of the last reference sample
+        self._mmd_ref = None
         if device == "cuda":
             self._init_gpu()
 
@@ -1009,6 +1021,108 @@ class ScoringEngine:
                 return gpu.forest_sweep(rows[0], rows[1], m, sw, jb, cut, want_curves)
 
         return run
+
+    # ------------------------------------------------------------ MMD drift
+    def mmd_drift(
+        self,
+        codes: np.ndarray,
+        nums: np.ndarray,
+        reference=None,
+        n_permutations: int = 100,
+        seed: int = 0,
+        cols_per_block: int | None = None,
+    ) -> dict:
+        """Multivariate drift of a batch against a reference sample: the
+        unbiased MMD^2 of whole embedded rows under one RBF kernel (median
+        heuristic on the reference), with a permutation p-value
+        (creditcore/mmd.py holds the exact statistic). Independent of the
+        classifier; one test, so the pack's ``drift_p_val`` is used with no
+        Bonferroni correction.
+
+        ``reference`` defaults to the pack's background sample
+        (ExplainUnavailable without one); ``(codes, nums)`` overrides it. The
+        heavy product W = K . ind runs in mmd_perm_kernel on a GPU engine and
+        in cpu_ref.mmd_perm_w_cpu on a CPU engine; everything else is shared
+        host code. Returns ``mmd2``, ``p_val``, ``is_drift``, ``threshold``
+        (the pack's drift_p_val), ``distance_threshold``, ``gamma``, ``n``,
+        ``n_ref``, ``n_permutations``. The scoring session is not touched.
+        Caps (creditcore/mmd.py) raise ExplainTooLarge."""
+        from . import mmd
+
+        p = self.packed
+        n_perm = mmd.check_permutations(n_permutations)
+        codes, nums = mmd.check_rows(codes, nums, "batch")
+        if len(codes) > mmd.MMD_MAX_ROWS:
+            raise ExplainTooLarge(
+                f"mmd_drift is capped at {mmd.MMD_MAX_ROWS} batch rows (got {len(codes)})"
+            )
+        if reference is None:
+            if p.bg_codes is None or p.bg_nums is None:
+                raise ExplainUnavailable(
+                    "model was packed without a background sample; re-train and "
+                    "re-pack, or pass reference=(codes, nums)"
+                )
+            reference = (p.bg_codes, p.bg_nums)
+        ref_codes, ref_nums = mmd.check_rows(reference[0], reference[1], "reference")
+        if len(ref_codes) > mmd.MMD_MAX_REFERENCE:
+            raise ExplainTooLarge(
+                f"mmd_drift is capped at {mmd.MMD_MAX_REFERENCE} reference rows "
+                f"(got {len(ref_codes)})"
+            )
+        n, m = len(codes), len(ref_codes)
+        with self._explain_lock:
+            mu, sd, z_ref, gamma = self._mmd_reference(ref_codes, ref_nums)
+            z = np.concatenate([mmd.embed(p, codes, nums, mu, sd), z_ref])
+            ind = mmd.indicator(n, m, n_perm, int(seed))
+            w = self._mmd_w(z, gamma, ind, cols_per_block)
+        out = mmd.decide(mmd.statistics(w, ind, n, m), float(p.drift_p_val))
+        out.update(gamma=gamma, n=n, n_ref=m, n_permutations=n_perm)
+        return out
+
+    def _mmd_reference(self, ref_codes: np.ndarray, ref_nums: np.ndarray):
+        """(mu, sd, z_ref, gamma) of a reference sample, kept for the last
+        sample seen; the caller holds _explain_lock."""
+        import hashlib
+
+        from . import mmd
+
+        key = hashlib.sha1(ref_codes.tobytes() + ref_nums.tobytes()).digest()
+        if self._mmd_ref is None or self._mmd_ref[0] != key:
+            mu, sd = mmd.reference_scale(self.packed, ref_nums)
+            z_ref = mmd.embed(self.packed, ref_codes, ref_nums, mu, sd)
+            self._mmd_ref = (key, mu, sd, z_ref, mmd.median_gamma(z_ref))
+        return self._mmd_ref[1:]
+
+    def _mmd_w(self, z: np.ndarray, gamma: float, ind: np.ndarray, cols_per_block=None):
+        """W = K . ind f64[N, Q] on this engine's device."""
+        from . import mmd
+
+        if self.device != "cuda":
+            return cpu_ref.mmd_perm_w_cpu(z, gamma, ind)
+        import torch
+
+        from .ops import gpu
+
+        dev = torch.device("cuda", self.device_index)
+        norms = mmd.squared_norms(z).astype(np.float32)
+        cols = int(cols_per_block or mmd.default_cols_per_block(len(z)))
+        with torch.cuda.device(dev):
+            return gpu.mmd_perm_w(
+                torch.from_numpy(mmd.pad_columns(z)).to(dev),
+                torch.from_numpy(norms).to(dev),
+                gamma,
+                torch.from_numpy(ind).to(dev),
+                cols,
+                launch_rows=int(self.MMD_LAUNCH_ROWS),
+            )
+
+    def mmd_drift_records(self, records, reference=None, **kw) -> dict:
+        """mmd_drift on a request body (list of dicts / DataFrame);
+        ``reference`` likewise, encoded with the same vocabulary."""
+        codes, nums = encode_batch(records, self.packed.vocabs)
+        if reference is not None:
+            reference = encode_batch(reference, self.packed.vocabs)
+        return self.mmd_drift(codes, nums, reference=reference, **kw)
 
     def counterfactual_records(self, records, **kw) -> dict:
         """counterfactuals on a request body (list of dicts / DataFrame)."""

@@ -1141,3 +1141,28 @@ def hrf_route_cpu(
         a, b = int(slot_off[t]), int(slot_off[t + 1])
         out[t] = hgbt_route_cpu(bins, table[a:b], node[t])
     return out
+
+
+def mmd_perm_w_cpu(
+    z: np.ndarray, gamma: float, ind: np.ndarray, max_bytes: int = 64 << 20
+) -> np.ndarray:
+    """``W = K . ind`` as f64[N, Q] of the MMD permutation test
+    (creditcore/mmd.py; mmd_perm_kernel on the GPU), in f64 throughout:
+    ``K[i, j] = exp(-gamma max(|z_i|^2 + |z_j|^2 - 2 z_i . z_j, 0))`` off the
+    diagonal and 0 on it. Row-chunked: it never holds more than ``max_bytes``
+    of K."""
+    z = np.asarray(z, dtype=np.float64)
+    ind = np.asarray(ind, dtype=np.float64)
+    n = len(z)
+    if z.ndim != 2 or ind.ndim != 2 or len(ind) != n:
+        raise ValueError("z must be [N, D] and ind [N, Q]")
+    norms = np.einsum("ij,ij->i", z, z)
+    w = np.empty((n, ind.shape[1]), dtype=np.float64)
+    step = max(1, int(max_bytes) // (8 * n))
+    for a in range(0, n, step):
+        b = min(a + step, n)
+        d2 = norms[a:b, None] + norms[None, :] - 2.0 * (z[a:b] @ z.T)
+        k = np.exp(-float(gamma) * np.maximum(d2, 0.0))
+        k[np.arange(b - a), np.arange(a, b)] = 0.0
+        w[a:b] = k @ ind
+    return w

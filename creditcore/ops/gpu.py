@@ -81,3 +81,19 @@ def forest_sweep(codes, nums, forest: dict, sweep: dict, jobs, cut: float, want_
     off = np.asarray(sweep["thr_off"])
     ends = np.cumsum(np.diff(off)[jobs[:, 1]] + 1)
     return rec, raw, np.split(flat.cpu().numpy(), ends[:-1])
+
+
+def mmd_perm_w(z, norms, gamma: float, ind, cols_per_block: int, launch_rows: int = 0):
+    """mmd_perm_w of the extension on device tensors (z f32[N, Dp], norms
+    f32[N], ind u8[N, Q]): W = K . ind as numpy f64[N, Q]. ``launch_rows``
+    > 0 runs it as several launches over slices of that many rows i (a
+    multiple of the 64-row tile)."""
+    import numpy as np
+
+    n = int(z.shape[0])
+    step = int(launch_rows) if launch_rows and launch_rows < n else n
+    parts = [
+        ext().mmd_perm_w(z, norms, float(gamma), ind, int(cols_per_block), a, min(step, n - a))
+        for a in range(0, n, step)
+    ]
+    return np.concatenate([p.cpu().numpy() for p in parts])  # D2H copies synchronize

@@ -254,6 +254,34 @@ class CounterfactualOutput(BaseModel):
     rows: list[CounterfactualRow]
 
 
+class MmdDriftRequest(BaseModel):
+    """POST /drift/mmd request: the records as /score takes them, the number
+    of permutations behind the p-value and the seed they are drawn from."""
+
+    records: list[dict]
+    n_permutations: int = 100
+    seed: int = 0
+
+    model_config = ConfigDict(extra="ignore")
+
+
+class MmdDriftOutput(BaseModel):
+    """POST /drift/mmd response: the unbiased MMD^2 of the batch against the
+    packed reference sample and its permutation p-value (``threshold`` is the
+    model's drift p-value, ``distance_threshold`` the permuted statistic at
+    that rank)."""
+
+    mmd2: float
+    p_val: float
+    is_drift: int
+    threshold: float
+    distance_threshold: float
+    gamma: float
+    n: int
+    n_ref: int
+    n_permutations: int
+
+
 # The one-record CI smoke-test fixture (reference app/sample-request.json).
 SAMPLE_REQUEST: list[dict] = [
     {

@@ -42,6 +42,8 @@ from .schema import (
     CounterfactualRequest,
     ExplainOutput,
     LoanApplicant,
+    MmdDriftOutput,
+    MmdDriftRequest,
     ModelOutput,
     PdpOutput,
     PdpRequest,
@@ -761,6 +763,70 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
                 for key in ("thresholds", "probabilities"):
                     if key in entry:
                         entry[key] = entry[key].tolist()
+        metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
+        return _json_response(out)
+
+    @app.post("/drift/mmd", response_model=MmdDriftOutput)
+    async def drift_mmd(req: MmdDriftRequest):
+        """Multivariate drift of the posted records against the model's
+        packed background sample: the MMD two-sample test on whole rows with a
+        permutation p-value (ScoringEngine.mmd_drift). Stateless: it neither
+        reads nor feeds GET /drift. One attempt on one live replica; bypasses
+        the micro-batcher."""
+        import asyncio
+
+        from .mmd import MMD_MAX_PERMUTATIONS, MMD_MAX_ROWS
+
+        metrics: Metrics = state["metrics"]
+        engines = state["engines"]
+        pool: ReplicaPool = state["pool"]
+        packed = engines[0].packed
+        if packed.bg_codes is None or packed.bg_nums is None:
+            raise HTTPException(
+                status_code=501,
+                detail="the served model was packed without a background sample; "
+                "re-train and re-pack it to enable /drift/mmd",
+            )
+        if len(req.records) > MMD_MAX_ROWS:
+            raise HTTPException(
+                status_code=413, detail=f"/drift/mmd takes at most {MMD_MAX_ROWS} rows"
+            )
+        if req.n_permutations > MMD_MAX_PERMUTATIONS:
+            raise HTTPException(
+                status_code=413,
+                detail=f"/drift/mmd takes at most {MMD_MAX_PERMUTATIONS} permutations",
+            )
+        if len(req.records) < 2:
+            raise HTTPException(status_code=422, detail="/drift/mmd needs at least two rows")
+        try:
+            codes, nums = encode_batch(req.records, packed.vocabs)
+        except (ValueError, TypeError, KeyError) as e:
+            raise HTTPException(status_code=422, detail=f"bad record: {e}")
+        try:
+            idx = pool.pick()
+        except RuntimeError:
+            metrics.observe_error()
+            raise HTTPException(status_code=503, detail="no healthy replicas")
+        t0 = time.perf_counter()
+
+        def call():
+            return engines[idx].mmd_drift(
+                codes, nums, n_permutations=req.n_permutations, seed=req.seed
+            )
+
+        try:
+            out = await asyncio.get_running_loop().run_in_executor(None, call)
+            pool.report_ok(idx)
+        except ExplainTooLarge as e:  # the request's fault, not the replica's
+            raise HTTPException(status_code=413, detail=str(e))
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        except ExplainUnavailable as e:
+            raise HTTPException(status_code=501, detail=str(e))
+        except Exception as e:
+            metrics.observe_error()
+            pool.report_fail(idx)
+            raise HTTPException(status_code=500, detail=f"mmd drift failed: {e}")
         metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
         return _json_response(out)
 

@@ -3496,6 +3496,254 @@ torch::Tensor ks_stats(
 }
 
 // ---------------------------------------------------------------------------
+// MMD permutation test (creditcore/mmd.py): W = K . ind without ever holding
+// the RBF Gram matrix K (4 GiB in f32 at 32,768 pooled rows). Both products
+// run on the matrix cores in f32 (v_mfma_f32_16x16x4_f32):
+//
+//   GEMM 1   S[j, i] = z_j . z_i            (transposed on purpose, see below)
+//   epilogue k[j, i] = exp(-gamma max(n_i + n_j - 2 S, 0)), 0 on the diagonal
+//   GEMM 2   Wt[q, i] += sum_j ind[j, q] k[j, i]
+//
+// A 256-thread block owns 64 rows i (16 per wave) and the columns
+// j in [y * cols_per_block, ...), walked in tiles of 64. Per tile the z rows
+// of both sides stream through LDS in 64-wide d-chunks (so D is not bounded
+// by registers) and the tile's indicator bytes sit in LDS, q-major, one dword
+// per four consecutive j.
+//
+// Operand layouts of the 16x16x4 f32 MFMA (lane l, h = l % 16, g = l / 16):
+// A holds A[h][k = g], B holds B[k = g][h], the accumulator register r holds
+// D[4 g + r][h]. With S computed as rows j x columns i a lane's four
+// accumulators are k[j = 4 g + r][i = h]; j is the summation index of GEMM 2
+// and its order inside the tile is free, so register r is fed unchanged as
+// the B operand of step r (summation slot g stands for j = 4 g + r) and the
+// A operand is ind[4 g + r][q = h]: byte r of the one dword the lane reads.
+// K never takes a trip through LDS to change layout. The same freedom is used
+// on d in GEMM 1: a lane reads d = 16 kk + 4 g .. + 3 of its row as one
+// float4 for four steps, on both operands alike.
+//
+// Every block writes its own f32 slab part[y][i][0 .. Qp): no atomics, no
+// pre-zeroed output; mmd_sum_kernel adds the slabs in f64 in split order, so
+// the result is bit-identical run to run.
+// ---------------------------------------------------------------------------
+
+#define MMD_BLOCK 256
+#define MMD_TILE 64       // rows i of a block; rows j of one step
+#define MMD_DC 64         // d-chunk staged in LDS
+#define MMD_ZLD 68        // LDS row stride of a z tile (floats): float4 reads
+                          // of 16 rows land on 16 distinct 4-bank groups
+#define MMD_ILD 17        // LDS row stride of the indicator tile (dwords)
+#define MMD_QT_MAX 16     // 16-wide q tiles: Qp <= 256
+#define MMD_MAX_POOLED 32768
+#define MMD_MAX_DP 4096
+
+// The MMD kernels are generated without packed f32 VALU instructions
+// (v_pk_fma_f32 and kin); per function, so that every other kernel of this
+// file keeps its code generation.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MMD_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define MMD_NO_PACKED_F32
+#endif
+
+typedef float mmd_f4 __attribute__((ext_vector_type(4)));
+
+MMD_NO_PACKED_F32 __global__ __launch_bounds__(MMD_BLOCK) void mmd_perm_kernel(
+    const float* __restrict__ z,        // [N, Dp]
+    const float* __restrict__ norms,    // [Np], 0 past N
+    const uint8_t* __restrict__ ind_t,  // [Qp, Np], 0 past Q and past N
+    float* __restrict__ part,           // [splits, rows, Qp]
+    int N, int Np, int Dp, int nqt, int cols_per_block, int row0, int rows,
+    float gamma)
+{
+  __shared__ __attribute__((aligned(16))) float zi_s[MMD_TILE * MMD_ZLD];
+  __shared__ __attribute__((aligned(16))) float zj_s[MMD_TILE * MMD_ZLD];
+  __shared__ unsigned ind_s[MMD_QT_MAX * 16 * MMD_ILD];
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int h = lane & 15, g = lane >> 4;
+  const int i_base = row0 + (int)blockIdx.x * MMD_TILE;
+  const int my_i = i_base + wave * 16 + h;
+  const int j_begin = (int)blockIdx.y * cols_per_block;
+  const int j_end = min(j_begin + cols_per_block, N);
+  const int Qp = nqt * 16;
+  const float n_i = norms[min(my_i, Np - 1)];
+  const bool i_ok = my_i < N;
+  // loader roles: a float4 column and four rows of each z tile per thread
+  const int ld_c = tid & 15, ld_r = tid >> 4;
+  // one d-chunk: the block's own rows are staged once, not once per j tile
+  const bool zi_once = Dp <= MMD_DC;
+
+  mmd_f4 acc[MMD_QT_MAX];
+#pragma unroll
+  for (int qt = 0; qt < MMD_QT_MAX; ++qt) acc[qt] = mmd_f4{0.f, 0.f, 0.f, 0.f};
+
+  for (int j0 = j_begin; j0 < j_end; j0 += MMD_TILE) {
+    mmd_f4 s[4];
+#pragma unroll
+    for (int js = 0; js < 4; ++js) s[js] = mmd_f4{0.f, 0.f, 0.f, 0.f};
+
+    for (int d0 = 0; d0 < Dp; d0 += MMD_DC) {
+      __syncthreads();  // the previous chunk (and tile) is consumed
+      const int d = d0 + 4 * ld_c;  // Dp % 4 == 0: d < Dp covers d + 3
+      const bool load_i = !zi_once || j0 == j_begin;  // uniform
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int row = ld_r + 16 * k;
+        const int gi = i_base + row, gj = j0 + row;
+        mmd_f4 vi = mmd_f4{0.f, 0.f, 0.f, 0.f}, vj = vi;
+        if (load_i && d < Dp && gi < N)
+          vi = *reinterpret_cast<const mmd_f4*>(z + (size_t)gi * Dp + d);
+        if (d < Dp && gj < N)
+          vj = *reinterpret_cast<const mmd_f4*>(z + (size_t)gj * Dp + d);
+        if (load_i)
+          *reinterpret_cast<mmd_f4*>(&zi_s[row * MMD_ZLD + 4 * ld_c]) = vi;
+        *reinterpret_cast<mmd_f4*>(&zj_s[row * MMD_ZLD + 4 * ld_c]) = vj;
+      }
+      if (d0 == 0) {
+        // indicator tile, q-major: 16 dwords (64 j) per q; j0 + 63 < Np
+        for (int q = ld_r; q < Qp; q += 16)
+          ind_s[q * MMD_ILD + ld_c] = *reinterpret_cast<const unsigned*>(
+              ind_t + (size_t)q * Np + j0 + 4 * ld_c);
+      }
+      __syncthreads();
+
+#pragma unroll
+      for (int kk = 0; kk < MMD_DC / 16; ++kk) {
+        if (d0 + kk * 16 >= Dp) continue;  // uniform
+        const mmd_f4 b = *reinterpret_cast<const mmd_f4*>(
+            &zi_s[(wave * 16 + h) * MMD_ZLD + kk * 16 + 4 * g]);
+#pragma unroll
+        for (int js = 0; js < 4; ++js) {
+          const mmd_f4 a = *reinterpret_cast<const mmd_f4*>(
+              &zj_s[(js * 16 + h) * MMD_ZLD + kk * 16 + 4 * g]);
+          s[js] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, s[js], 0, 0, 0);
+          s[js] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, s[js], 0, 0, 0);
+          s[js] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, s[js], 0, 0, 0);
+          s[js] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, s[js], 0, 0, 0);
+        }
+      }
+    }
+
+    // epilogue on the accumulators, then GEMM 2 straight from them
+#pragma unroll
+    for (int js = 0; js < 4; ++js) {
+      const int jr = j0 + js * 16 + 4 * g;  // register r is row jr + r
+      const mmd_f4 n_j = *reinterpret_cast<const mmd_f4*>(norms + jr);
+      mmd_f4 kv;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float d2 = fmaxf(n_i + n_j[r] - 2.0f * s[js][r], 0.0f);
+        const float k = expf(-gamma * d2);
+        kv[r] = (i_ok && jr + r < N && jr + r != my_i) ? k : 0.0f;
+      }
+#pragma unroll
+      for (int qt = 0; qt < MMD_QT_MAX; ++qt) {
+        if (qt >= nqt) continue;  // uniform; keeps acc[] in registers
+        const unsigned u = ind_s[(qt * 16 + h) * MMD_ILD + js * 4 + g];
+        acc[qt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            (float)(u & 0xffu), kv[0], acc[qt], 0, 0, 0);
+        acc[qt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            (float)((u >> 8) & 0xffu), kv[1], acc[qt], 0, 0, 0);
+        acc[qt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            (float)((u >> 16) & 0xffu), kv[2], acc[qt], 0, 0, 0);
+        acc[qt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            (float)(u >> 24), kv[3], acc[qt], 0, 0, 0);
+      }
+    }
+  }
+
+  // acc[qt][r] is Wt[q = 16 qt + 4 g + r][i = my_i]: one float4 per q tile
+  if (i_ok && my_i < row0 + rows) {
+    float* out = part + ((size_t)blockIdx.y * rows + (my_i - row0)) * Qp + 4 * g;
+#pragma unroll
+    for (int qt = 0; qt < MMD_QT_MAX; ++qt) {
+      if (qt >= nqt) continue;
+      *reinterpret_cast<mmd_f4*>(out + qt * 16) = acc[qt];
+    }
+  }
+}
+
+// W[i, q] = sum over splits of part[s, i, q], added in f64 in split order.
+MMD_NO_PACKED_F32 __global__ __launch_bounds__(BLOCK) void mmd_sum_kernel(
+    const float* __restrict__ part, double* __restrict__ w,
+    int splits, long long rows, int Q, int Qp)
+{
+  const long long e = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (e >= rows * Q) return;
+  const long long i = e / Q;
+  const int q = (int)(e - i * Q);
+  double sum = 0.0;
+  for (int s = 0; s < splits; ++s)
+    sum += (double)part[((size_t)s * rows + i) * Qp + q];
+  w[e] = sum;
+}
+
+// W[row_begin .. row_begin + row_count) of K . ind as f64[row_count, Q].
+// z f32[N, Dp] (D zero-padded to a multiple of 4), norms f32[N] the squared
+// row norms, ind u8[N, Q] of 0/1. row_count < 0 takes every row from
+// row_begin on; a slice lets the caller split a long launch over the i tiles.
+torch::Tensor mmd_perm_w(torch::Tensor z, torch::Tensor norms, double gamma,
+                         torch::Tensor ind, int64_t cols_per_block,
+                         int64_t row_begin, int64_t row_count)
+{
+  TORCH_CHECK(z.is_cuda() && z.scalar_type() == torch::kFloat32 &&
+              z.dim() == 2 && z.is_contiguous(),
+              "z must be a contiguous f32[N, Dp] GPU tensor");
+  const int64_t N = z.size(0), Dp = z.size(1);
+  TORCH_CHECK(N >= 2 && N <= MMD_MAX_POOLED, "pooled rows out of range: ", N);
+  TORCH_CHECK(Dp >= 4 && Dp % 4 == 0 && Dp <= MMD_MAX_DP,
+              "Dp must be a multiple of 4 in [4, ", MMD_MAX_DP, "]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(z.data_ptr<float>()) % 16 == 0,
+              "z must be 16-byte aligned (rows are read as float4)");
+  TORCH_CHECK(norms.is_cuda() && norms.device() == z.device() &&
+              norms.scalar_type() == torch::kFloat32 && norms.dim() == 1 &&
+              norms.size(0) == N && norms.is_contiguous(),
+              "norms must be a contiguous f32[N] tensor on z's GPU");
+  TORCH_CHECK(ind.is_cuda() && ind.device() == z.device() &&
+              ind.scalar_type() == torch::kUInt8 && ind.dim() == 2 &&
+              ind.size(0) == N && ind.is_contiguous(),
+              "ind must be a contiguous u8[N, Q] tensor on z's GPU");
+  const int64_t Q = ind.size(1);
+  TORCH_CHECK(Q >= 1 && Q <= MMD_QT_MAX * 16,
+              "Q = P + 2 must be at most ", MMD_QT_MAX * 16, " (P <= 254)");
+  TORCH_CHECK(cols_per_block >= MMD_TILE && cols_per_block % MMD_TILE == 0,
+              "cols_per_block must be a positive multiple of ", MMD_TILE);
+  TORCH_CHECK(std::isfinite(gamma) && gamma > 0.0, "gamma must be positive");
+  if (row_count < 0) row_count = N - row_begin;
+  TORCH_CHECK(row_begin >= 0 && row_begin % MMD_TILE == 0 && row_count >= 1 &&
+              row_begin + row_count <= N,
+              "row slice must start on a tile and lie inside [0, N)");
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)z.get_device());
+  const int64_t Np = (N + MMD_TILE - 1) / MMD_TILE * MMD_TILE;
+  const int64_t nqt = (Q + 15) / 16, Qp = nqt * 16;
+  const int64_t splits = (N + cols_per_block - 1) / cols_per_block;
+  // padded operands: the kernel reads whole tiles of these two unchecked
+  auto norms_p = torch::zeros({Np}, norms.options());
+  norms_p.slice(0, 0, N).copy_(norms);
+  auto ind_t = torch::zeros({Qp, Np}, ind.options());
+  ind_t.slice(0, 0, Q).slice(1, 0, N).copy_(ind.t());
+  auto part = torch::empty({splits, row_count, Qp}, z.options());
+  auto w = torch::empty({row_count, Q}, z.options().dtype(torch::kFloat64));
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(mmd_perm_kernel,
+      dim3((unsigned)((row_count + MMD_TILE - 1) / MMD_TILE), (unsigned)splits),
+      dim3(MMD_BLOCK), 0, stream,
+      z.data_ptr<float>(), norms_p.data_ptr<float>(), ind_t.data_ptr<uint8_t>(),
+      part.data_ptr<float>(), (int)N, (int)Np, (int)Dp, (int)nqt,
+      (int)cols_per_block, (int)row_begin, (int)row_count, (float)gamma);
+  HIP_CHECK(hipGetLastError());
+  const int64_t total = row_count * Q;
+  hipLaunchKernelGGL(mmd_sum_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)),
+      dim3(BLOCK), 0, stream, part.data_ptr<float>(), w.data_ptr<double>(),
+      (int)splits, (long long)row_count, (int)Q, (int)Qp);
+  HIP_CHECK(hipGetLastError());
+  return w;
+}
+
+// ---------------------------------------------------------------------------
 // ScoreSession — one replica's resident GPU state + a single-call scoring
 // path. Owns the model buffers in HBM, a private HIP stream, device
 // workspace and pinned staging, so one Python call per request performs:
@@ -4900,6 +5148,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("HRF_MAX_FEATS") = py::int_(HRF_MAX_FEATS);
   m.def("drift_stats", &drift_stats,
         "Per-feature drift statistics: categorical histograms + K-S D (gfx950)");
+  m.def("mmd_perm_w", &mmd_perm_w,
+        "MMD permutation test: W = K . ind as f64[rows, Q], the RBF Gram "
+        "matrix K fused away on the matrix cores (gfx950)",
+        py::arg("z"), py::arg("norms"), py::arg("gamma"), py::arg("ind"),
+        py::arg("cols_per_block"), py::arg("row_begin") = 0,
+        py::arg("row_count") = -1);
+  m.attr("MMD_TILE") = py::int_(MMD_TILE);
   m.def("encode_records", &encode_records,
         "Native request encoder: list[dict] -> (codes i16[B,9], nums f32[B,14])");
   m.def("encode_json", &encode_json,
