@@ -1046,7 +1046,9 @@ class ScoringEngine:
         host code. Returns ``mmd2``, ``p_val``, ``is_drift``, ``threshold``
         (the pack's drift_p_val), ``distance_threshold``, ``gamma``, ``n``,
         ``n_ref``, ``n_permutations``. The scoring session is not touched.
-        Caps (creditcore/mmd.py) raise ExplainTooLarge."""
+        Caps (creditcore/mmd.py) raise ExplainTooLarge; an infinite numeric,
+        or rows whose embedding or squared norm is not finite in f32, raise
+        ValueError naming the side (NaN numerics are imputed)."""
         from . import mmd
 
         p = self.packed
@@ -1072,7 +1074,8 @@ class ScoringEngine:
         n, m = len(codes), len(ref_codes)
         with self._explain_lock:
             mu, sd, z_ref, gamma = self._mmd_reference(ref_codes, ref_nums)
-            z = np.concatenate([mmd.embed(p, codes, nums, mu, sd), z_ref])
+            z_batch = mmd.check_embedding(mmd.embed(p, codes, nums, mu, sd), "batch")
+            z = np.concatenate([z_batch, z_ref])
             ind = mmd.indicator(n, m, n_perm, int(seed))
             w = self._mmd_w(z, gamma, ind, cols_per_block)
         out = mmd.decide(mmd.statistics(w, ind, n, m), float(p.drift_p_val))
@@ -1090,6 +1093,7 @@ class ScoringEngine:
         if self._mmd_ref is None or self._mmd_ref[0] != key:
             mu, sd = mmd.reference_scale(self.packed, ref_nums)
             z_ref = mmd.embed(self.packed, ref_codes, ref_nums, mu, sd)
+            mmd.check_embedding(z_ref, "reference")  # before it can be cached
             self._mmd_ref = (key, mu, sd, z_ref, mmd.median_gamma(z_ref))
         return self._mmd_ref[1:]
 

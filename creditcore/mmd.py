@@ -35,7 +35,25 @@ def check_rows(codes, nums, what: str):
         raise ValueError(f"{what} must be (codes [R, {N_CAT}], nums [R, {N_NUM}])")
     if r < 2:
         raise ValueError(f"mmd_drift needs at least two {what} rows (got {r})")
+    if np.isinf(nums).any():  # NaN is a missing value and is imputed
+        raise ValueError(f"{what} rows hold an infinite numeric")
     return codes, nums
+
+
+def check_embedding(z: np.ndarray, what: str) -> np.ndarray:
+    """z unchanged, or ValueError naming the side: every entry of the f32
+    embedding and every squared row norm, once cast to f32 (what the kernel is
+    given), must be finite. A NaN distance would otherwise read as 0 in the
+    kernel (fmaxf) and as NaN in the f64 reference."""
+    if not np.isfinite(z).all():
+        raise ValueError(f"{what} rows do not embed to finite f32 values")
+    with np.errstate(over="ignore"):
+        n32 = squared_norms(z).astype(np.float32)
+    if not np.isfinite(n32).all():
+        raise ValueError(
+            f"{what} rows embed too far from the reference: a squared norm overflows f32"
+        )
+    return z
 
 
 def check_permutations(n_permutations) -> int:
@@ -73,7 +91,8 @@ def embed(packed: PackedModel, codes: np.ndarray, nums: np.ndarray, mu, sd) -> n
     code = np.asarray(packed.feat_code[:n_oh])
     z[:, :n_oh] = (np.asarray(codes)[:, col] == code[None, :]) * _ONE_HOT
     x = impute(packed, nums).astype(np.float64)
-    z[:, n_oh:] = ((x - mu[None, :]) / sd[None, :]).astype(np.float32)
+    with np.errstate(over="ignore"):  # an overflow is refused by check_embedding
+        z[:, n_oh:] = ((x - mu[None, :]) / sd[None, :]).astype(np.float32)
     return z
 
 

@@ -80,6 +80,39 @@ def test_engine_reference_override_and_checks(packed, score_batch):
         eng.mmd_drift(codes, nums, n_permutations=mmd.MMD_MAX_PERMUTATIONS + 1)
 
 
+def test_engine_refuses_non_finite_rows(packed, score_batch):
+    """inf, -inf and an embedding that overflows f32 raise ValueError naming
+    the side and leave the reference cache as it was; NaN is still imputed
+    (the same assertions run on a GPU engine in test_mmd_kernels_gpu.py)."""
+    from _mmd_cases import check_engine_refuses_non_finite
+
+    codes, nums = encode_batch(score_batch.iloc[:40], packed.vocabs)
+    check_engine_refuses_non_finite(ScoringEngine(packed, device="cpu"), packed, codes, nums)
+
+
+def test_route_refuses_non_finite_rows(model_dir, score_batch):
+    """A numeric that is infinite once it is f32, or that embeds past f32's
+    range, is a 422 like mmd_drift's other ValueErrors, and the replica goes
+    on serving."""
+    from fastapi.testclient import TestClient
+
+    from creditcore import serve
+    from creditcore.config import ServeConfig
+
+    cfg = ServeConfig()
+    cfg.model_directory = model_dir
+    cfg.device = "cpu"
+    records = score_batch.iloc[4:36].to_dict(orient="records")
+    with TestClient(serve.create_app(cfg)) as client:
+        for value in (1e300, -1e300, 3.0e38):
+            bad = [dict(r) for r in records]
+            bad[7]["bill_amount_2"] = value
+            r = client.post("/drift/mmd", json={"records": bad, "n_permutations": 10})
+            assert r.status_code == 422 and "batch" in r.json()["detail"], r.text
+        r = client.post("/drift/mmd", json={"records": records, "n_permutations": 10})
+        assert r.status_code == 200 and np.isfinite(r.json()["mmd2"])
+
+
 def test_route(model_dir, packed, score_batch):
     from fastapi.testclient import TestClient
 
