@@ -8,6 +8,7 @@ Replaces the reference's Databricks bundle + GitHub Actions + Bicep pipeline
     python -m creditcore serve  [--model-directory ./model] [--port 5000] ...
     python -m creditcore smoke  [--url http://127.0.0.1:5000]
     python -m creditcore pdp    --model-directory ./model --features credit_limit,age --out pdp.json
+    python -m creditcore ale    --model-directory ./model --features bill_amount_3,age --out ale.json
     python -m creditcore counterfactual --model-directory ./model --data rows.csv --out cf.json
     python -m creditcore drift-mmd --model-directory ./model --data batch.csv [--reference ref.csv]
 """
@@ -293,6 +294,53 @@ def _cmd_pdp(argv):
                       "sample_rows": doc["sample_rows"], "device": eng.device}))
 
 
+def _cmd_ale(argv):
+    """Offline model-validation artefact: accumulated local effects of the
+    numeric features of a packaged model, written as JSON."""
+    p = argparse.ArgumentParser(prog="creditcore ale")
+    p.add_argument("--model-directory", default="./model")
+    p.add_argument("--features", required=True,
+                   help="comma-separated numeric feature names (bill_amount_3,age)")
+    p.add_argument("--data", default=None,
+                   help="CSV rows (the train --data schema) that replace the "
+                        "model's packed background sample; at most 65536 rows")
+    p.add_argument("--grid-resolution", type=int, default=20)
+    p.add_argument("--kind", default="average", choices=["average", "both"])
+    p.add_argument("--response", default="probability", choices=["probability", "raw"])
+    p.add_argument("--device", default="auto")
+    p.add_argument("--out", default=None)
+    a = p.parse_args(argv)
+    from .engine import load_engine
+    from .pack import encode_batch
+
+    eng = load_engine(a.model_directory, device=a.device)
+    sample = None
+    if a.data:
+        import pandas as pd
+
+        sample = encode_batch(pd.read_csv(a.data), eng.packed.vocabs)
+    out = eng.accumulated_local_effects(
+        [n.strip() for n in a.features.split(",")], sample=sample,
+        grid_resolution=a.grid_resolution, kind=a.kind, response=a.response,
+    )
+    doc = {
+        "output_space": out["output_space"],
+        "sample_rows": int(out["sample_rows"]),
+        "kind": a.kind,
+        "results": [
+            {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in res.items()}
+            for res in out["results"]
+        ],
+    }
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(doc, f)
+        print(json.dumps({"out": a.out, "entries": len(doc["results"]),
+                          "sample_rows": doc["sample_rows"], "device": eng.device}))
+    else:
+        print(json.dumps(doc))
+
+
 def _cmd_counterfactual(argv):
     """Offline single-feature counterfactuals of CSV rows under a packaged
     model, written as JSON (ScoringEngine.counterfactuals)."""
@@ -395,6 +443,7 @@ def main():
         "score-batch": _cmd_score_batch,
         "generate-data": _cmd_generate_data,
         "pdp": _cmd_pdp,
+        "ale": _cmd_ale,
         "counterfactual": _cmd_counterfactual,
         "drift-mmd": _cmd_drift_mmd,
     }

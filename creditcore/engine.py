@@ -178,6 +178,19 @@ class ScoringEngine:
     # profiles/bench_results/pdp_micro.txt. The largest call the caps allow
     # (10.7 M pairs) runs as six launches.
     PDP_LAUNCH_PAIRS = 2097152
+    # accumulated_local_effects: most (row, entry) pairs of one forest_ale
+    # launch (a pair is one dual walk of the whole forest, between one and
+    # two plain walks); a call above it runs as several launches over entry
+    # and row slices. Sized like PDP_LAUNCH_PAIRS: the largest measured pair
+    # count whose launch on the flagship forest (RF 500 x depth 16, all 14
+    # numeric features at grid_resolution 20) is no longer than 1.25 x the
+    # method="shap" launch at SHAP_MAX_ROWS measured in the same run:
+    # forest_shap at 1024 rows 60.26 ms (bound 75.32 ms), forest_ale at
+    # 65,536 rows x 14 entries = 917,504 pairs 27.62 ms on an MI355X (256
+    # rows: 5.78 ms, 16,384 rows: 7.31 ms), bench/ale_micro.py,
+    # profiles/bench_results/ale_micro.txt. That is the largest call the caps
+    # allow (ALE_MAX_ROWS x N_NUM), so today no call is sliced.
+    ALE_LAUNCH_JOBS = 917504
     # counterfactuals: most {row, numeric column} jobs of one forest_sweep
     # launch; a call above it runs as several launches over job slices. Held
     # against the method="shap" launch at SHAP_MAX_ROWS measured in the same
@@ -827,6 +840,162 @@ class ScoringEngine:
                     torch.from_numpy(np.ascontiguousarray(jb, dtype=np.int32)),
                 )
                 return out.cpu().numpy()  # D2H copy synchronizes the stream
+
+        return run
+
+    # ------------------------------------------- accumulated local effects
+    def accumulated_local_effects(
+        self,
+        features,
+        sample=None,
+        grid_resolution: int = 20,
+        grid: dict | None = None,
+        kind: str = "average",
+        response: str = "probability",
+    ) -> dict:
+        """Accumulated local effects (ALE) of the classifier output on numeric
+        features: every row of a sample is moved only across the grid
+        interval its own value lies in, the differences are averaged per
+        interval and accumulated, and the curve is centred (creditcore/ale.py
+        states the estimator in full). Unlike partial dependence, no row is
+        scored away from the values it was observed with, which matters for
+        strongly correlated columns.
+
+        ``features`` lists numeric feature names (a categorical name is a
+        ValueError). ``sample`` is an encoded ``(codes, nums)`` pair and
+        defaults to the packed background sample. Edges are the sample
+        quantiles at ``grid_resolution`` equal steps unless ``grid={name:
+        edges}`` gives them (rows outside clamp into the first or last
+        interval). ``response="raw"`` (gradient boosting only) works in
+        log-odds.
+
+        Returns ``{"results": [...], "sample_rows", "output_space"}``; each
+        result holds ``feature``, ``edges`` (Ke + 1 floats), ``ale`` f64[Ke +
+        1], ``counts`` i64[Ke] and, with ``kind="both"``, the per-row
+        ``interval`` i32[R] (1..Ke) and ``local_effect`` f64[R]. A constant
+        column has one edge, ``ale = [0.0]`` and ``counts = [R]``. The
+        scoring session is not touched. Caps (creditcore/ale.py) raise
+        ExplainTooLarge."""
+        from . import ale
+
+        p = self.packed
+        if kind not in ale.ALE_KINDS:
+            raise ValueError(f"kind must be one of {ale.ALE_KINDS} (got {kind!r})")
+        if response not in ale.ALE_RESPONSES:
+            raise ValueError(f"response must be one of {ale.ALE_RESPONSES} (got {response!r})")
+        cls_kind = int(getattr(p, "cls_kind", 0))
+        if response == "raw" and cls_kind != 1:
+            raise ValueError("response='raw' applies to the log-odds (boosted) families only")
+        own = sample is None  # the packed sample: its device copy is kept
+        try:
+            names = ale.parse_features(features)
+            res, overrides = ale.check_args(grid_resolution, grid)
+            if own:
+                if p.bg_codes is None or p.bg_nums is None:
+                    raise ExplainUnavailable(
+                        "model was packed without a background sample; re-train and "
+                        "re-pack it (or pass sample=) to enable accumulated local effects"
+                    )
+                sample = (p.bg_codes, p.bg_nums)
+            codes = np.ascontiguousarray(sample[0], dtype=np.int16)
+            nums = np.ascontiguousarray(sample[1], dtype=np.float32)
+            r = len(codes)
+            if codes.shape != (r, N_CAT) or nums.shape != (r, N_NUM):
+                raise ValueError(f"sample must be (codes [R, {N_CAT}], nums [R, {N_NUM}])")
+            if r < 1:
+                raise ValueError("the sample must have at least one row")
+            if r > ale.ALE_MAX_ROWS:
+                raise ale.AleTooLarge(
+                    f"the sample is capped at {ale.ALE_MAX_ROWS} rows (got {r})"
+                )
+            nums_imp = cpu_ref.impute_nums(p, nums)
+            edges_of = {}
+            for n in names:
+                if n not in edges_of:
+                    edges_of[n] = (
+                        ale.override_edges(n, overrides[n])
+                        if n in overrides
+                        else ale.quantile_edges(nums_imp[:, FEATURES.index(n) - N_CAT], res)
+                    )
+        except ale.AleTooLarge as e:
+            raise ExplainTooLarge(str(e)) from None
+        # constant columns (one edge) are answered here, not by the kernel
+        sent = [i for i, n in enumerate(names) if len(edges_of[n]) > 1]
+        players = np.array([FEATURES.index(names[i]) for i in sent], dtype=np.int32)
+        interval = np.empty((len(sent), r), dtype=np.int32)
+        sums = np.empty((len(sent), r, 2), dtype=np.float64)
+        # One launch covers at most ALE_LAUNCH_JOBS (row, entry) pairs: whole
+        # entries over a row slice, as many as fit.
+        rows_step = max(1, min(r, int(self.ALE_LAUNCH_JOBS)))
+        ent_step = max(1, int(self.ALE_LAUNCH_JOBS) // rows_step)
+        with self._explain_lock:
+            if sent:
+                if self.device == "cuda":
+                    run = self._ale_gpu(codes, nums, own)
+                else:
+                    def run(a, b, pl, off, z):
+                        return cpu_ref.forest_ale_cpu(p, codes[a:b], nums_imp[a:b], pl, off, z)
+            for e in range(0, len(sent), ent_step):
+                off, z = ale.edge_table([edges_of[names[i]] for i in sent[e : e + ent_step]])
+                for a in range(0, r, rows_step):
+                    b = min(a + rows_step, r)
+                    interval[e : e + ent_step, a:b], sums[e : e + ent_step, a:b] = run(
+                        a, b, players[e : e + ent_step], off, z
+                    )
+        results, slot = [], {i: s for s, i in enumerate(sent)}
+        for i, n in enumerate(names):
+            z = edges_of[n]
+            out = {"feature": n, "edges": [float(v) for v in z]}
+            if i in slot:
+                s = slot[i]
+                curve, counts, local = ale.finish(
+                    interval[s], sums[s], len(z) - 1, cls_kind, float(p.cls_bias),
+                    int(p.cls_n_trees), response,
+                )
+                rows_k = interval[s]
+            else:
+                curve, counts = np.zeros(1), np.array([r], dtype=np.int64)
+                local, rows_k = np.zeros(r), np.zeros(r, dtype=np.int32)
+            out["ale"], out["counts"] = curve, counts
+            if kind == "both":
+                out["interval"], out["local_effect"] = rows_k.copy(), local
+            results.append(out)
+        return {
+            "results": results,
+            "sample_rows": r,
+            "output_space": "log_odds" if response == "raw" else "probability",
+        }
+
+    def _ale_gpu(self, codes: np.ndarray, nums: np.ndarray, own: bool):
+        """One-launch runner of forest_ale on the device (row slice and edge
+        table in, numpy (interval, sums) out); the caller holds
+        _explain_lock. Tables and sample as _whatif_gpu keeps them."""
+        import torch
+
+        ext = self._gpu["ext"]
+        dev = torch.device("cuda", self.device_index)
+        m = self._forest_dev()
+        smp = self._pdp_sample_dev if own else None
+        if smp is None:
+            smp = (torch.from_numpy(codes).to(dev), torch.from_numpy(nums).to(dev))
+            if own:
+                self._pdp_sample_dev = smp
+
+        def run(a: int, b: int, players: np.ndarray, edge_off: np.ndarray, edges: np.ndarray):
+            with torch.cuda.device(dev):
+                interval, sums = ext.forest_ale(
+                    smp[0][a:b],
+                    smp[1][a:b],
+                    m["cls_nodes"],
+                    m["cls_off"],
+                    m["feat_col"],
+                    m["feat_code"],
+                    m["medians"],
+                    torch.from_numpy(np.ascontiguousarray(players, dtype=np.int32)),
+                    torch.from_numpy(np.ascontiguousarray(edge_off, dtype=np.int32)),
+                    torch.from_numpy(np.ascontiguousarray(edges, dtype=np.float32)),
+                )
+                return interval.cpu().numpy(), sums.cpu().numpy()  # D2H copies synchronize
 
         return run
 

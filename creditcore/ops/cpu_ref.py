@@ -156,6 +156,58 @@ def forest_whatif_cpu(
     return out
 
 
+def forest_ale_cpu(
+    packed: PackedModel,
+    codes: np.ndarray,
+    nums_imp: np.ndarray,
+    players: np.ndarray,
+    edge_off: np.ndarray,
+    edges: np.ndarray,
+):
+    """Accumulated local effects, the reference of forest_ale_kernel:
+    ``(interval i32[E, R], sums f64[E, R, 2])``. Entry e sweeps the numeric
+    schema feature ``players[e]`` over the ascending f32 edges
+    ``z = edges[edge_off[e]:edge_off[e + 1]]`` (Ke + 1 of them, at least 2):
+    a row with (imputed) value x lies in interval
+    ``k = clip(#{z < x}, 1, Ke)``, i.e. (z[k-1], z[k]] with both ends
+    clamped, and ``sums[e, r]`` holds the raw classifier sums of row r with
+    the column set to z[k-1] and to z[k]. Deliberately the dumb version:
+    forest_whatif_cpu, two one-row jobs per (row, entry); the rows of one
+    interval share their two jobs, which changes no row's sums."""
+    codes = np.ascontiguousarray(codes, dtype=np.int16)
+    nums_imp = np.ascontiguousarray(nums_imp, dtype=np.float32)
+    players = np.asarray(players, dtype=np.int64).reshape(-1)
+    edge_off = np.asarray(edge_off, dtype=np.int64).reshape(-1)
+    edges = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1)
+    n_ent, r = len(players), len(codes)
+    if n_ent < 1 or r < 1:
+        raise ValueError("forest_ale needs at least one entry and one row")
+    if ((players < N_CAT) | (players >= N_CAT + N_NUM)).any():
+        raise ValueError("ALE players must be numeric features")
+    if len(edge_off) != n_ent + 1 or edge_off[0] != 0 or edge_off[-1] != len(edges):
+        raise ValueError("edge_off does not span edges")
+    interval = np.empty((n_ent, r), dtype=np.int32)
+    sums = np.empty((n_ent, r, 2), dtype=np.float64)
+    step = max(1, (1 << 20) // max(1, int(packed.cls_n_trees)))
+    for e, player in enumerate(players):
+        z = edges[edge_off[e] : edge_off[e + 1]]
+        if len(z) < 2 or not np.isfinite(z).all() or not (np.diff(z) > 0).all():
+            raise ValueError("an entry needs at least 2 finite, strictly ascending edges")
+        x = nums_imp[:, player - N_CAT]
+        k = np.clip((z[None, :] < x[:, None]).sum(axis=1), 1, len(z) - 1)
+        interval[e] = k
+        for kk in np.unique(k):
+            rows = np.flatnonzero(k == kk)
+            jobs = np.array(
+                [[player, z[kk - 1].view(np.int32), -1, 0], [player, z[kk].view(np.int32), -1, 0]],
+                dtype=np.int32,
+            )
+            for a in range(0, len(rows), step):  # bounds the traversal's arrays
+                part = rows[a : a + step]
+                sums[e, part] = forest_whatif_cpu(packed, codes[part], nums_imp[part], jobs).T
+    return interval, sums
+
+
 def forest_sweep_cpu(
     packed: PackedModel,
     codes: np.ndarray,

@@ -194,6 +194,46 @@ class PdpOutput(BaseModel):
     results: list[PdpCurve]
 
 
+class AleRequest(BaseModel):
+    """POST /explain/ale request. ``features`` are numeric feature names;
+    ``grid`` optionally replaces the quantile edges of a feature with at
+    least 2 strictly ascending numbers."""
+
+    features: list[str]
+    grid_resolution: int = 20
+    kind: str = "average"
+    response: str = "probability"
+    grid: dict[str, list[float]] | None = None
+
+    model_config = ConfigDict(extra="ignore")
+
+
+class AleCurve(BaseModel):
+    """Accumulated local effects of the classifier on one numeric feature:
+    ``ale[k]`` is the centred effect at ``edges[k]`` and ``counts[k]`` the
+    sample rows in interval (edges[k], edges[k+1]] (a constant column has one
+    edge, ``ale = [0.0]`` and all rows in ``counts[0]``). With
+    ``kind="both"``, ``interval`` (1-based) and ``local_effect`` per row."""
+
+    feature: str
+    edges: list[float]
+    ale: list[float]
+    counts: list[int]
+    interval: list[int] | None = None
+    local_effect: list[float] | None = None
+
+
+class AleOutput(BaseModel):
+    """POST /explain/ale response: one curve per requested feature, computed
+    on the model's ``sample_rows`` background rows, in ``output_space``
+    ("probability", or "log_odds" with ``response="raw"``)."""
+
+    output_space: str
+    sample_rows: int
+    kind: str
+    results: list[AleCurve]
+
+
 class CounterfactualRequest(BaseModel):
     """POST /explain/counterfactual request: the records as /explain takes
     them, the features to move (default: all), the decision threshold on the

@@ -38,6 +38,8 @@ from .engine import (
 from .pack import encode_batch
 from .schema import (
     FEATURES,
+    AleOutput,
+    AleRequest,
     CounterfactualOutput,
     CounterfactualRequest,
     ExplainOutput,
@@ -705,6 +707,66 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
             "sample_rows": int(out["sample_rows"]),
             "kind": req.kind,
             "results": results,
+        }
+        metrics.observe_request(int(out["sample_rows"]), (time.perf_counter() - t0) * 1e3)
+        return _json_response(payload)
+
+    @app.post("/explain/ale", response_model=AleOutput)
+    async def explain_ale(req: AleRequest):
+        """Accumulated local effects of the classifier on numeric features,
+        computed on the model's packed background sample: every sample row
+        is moved only across the quantile interval its own value lies in, so
+        correlated columns are never scored off the data. One attempt on one
+        live replica; bypasses the micro-batcher."""
+        import asyncio
+
+        metrics: Metrics = state["metrics"]
+        engines = state["engines"]
+        pool: ReplicaPool = state["pool"]
+        packed = engines[0].packed
+        if packed.bg_codes is None or packed.bg_nums is None:
+            raise HTTPException(
+                status_code=501,
+                detail="the served model was packed without a background sample; "
+                "re-train and re-pack it to enable /explain/ale",
+            )
+        try:
+            idx = pool.pick()
+        except RuntimeError:
+            metrics.observe_error()
+            raise HTTPException(status_code=503, detail="no healthy replicas")
+        t0 = time.perf_counter()
+
+        def call():
+            return engines[idx].accumulated_local_effects(
+                req.features,
+                grid_resolution=req.grid_resolution,
+                grid=req.grid,
+                kind=req.kind,
+                response=req.response,
+            )
+
+        try:
+            out = await asyncio.get_running_loop().run_in_executor(None, call)
+            pool.report_ok(idx)
+        except ExplainTooLarge as e:  # the request's fault, not the replica's
+            raise HTTPException(status_code=413, detail=str(e))
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        except ExplainUnavailable as e:
+            raise HTTPException(status_code=501, detail=str(e))
+        except Exception as e:
+            metrics.observe_error()
+            pool.report_fail(idx)
+            raise HTTPException(status_code=500, detail=f"accumulated local effects failed: {e}")
+        payload = {
+            "output_space": out["output_space"],
+            "sample_rows": int(out["sample_rows"]),
+            "kind": req.kind,
+            "results": [
+                {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in res.items()}
+                for res in out["results"]
+            ],
         }
         metrics.observe_request(int(out["sample_rows"]), (time.perf_counter() - t0) * 1e3)
         return _json_response(payload)

@@ -1036,6 +1036,207 @@ __global__ __launch_bounds__(WHATIF_BLOCK) void forest_whatif_kernel(
   }
 }
 
+// Accumulated local effects (ALE): per (row, entry) the raw classifier sum of
+// the row with ONE numeric column set to the lower and to the upper edge of the
+// grid interval the row's own value lies in. An entry is {numeric player, its
+// ascending f32 edges z[0..Ke]}; interval k = clip(#{z < x}, 1, Ke) is
+// (z[k-1], z[k]], found by the thread itself with f32 compares (a binary
+// search over the entry's edges, staged in LDS once per block and entry; the
+// host sends no per-row table). Outputs: interval[e, row] = k and
+// sums[e, row] = {S at z[k-1], S at z[k]}, each the tree-order f64 sum that
+// forest_whatif_kernel gives for that value, bit for bit.
+//
+// Work split as forest_whatif_kernel: one thread owns a (row, entry) pair and
+// all of its trees, one wave per block, rows staged column-major in LDS with
+// fused imputation (own slots only), blockIdx.y strides over the entries. The
+// only shared LDS is the edge list, hence the two barriers per entry; they
+// are why no thread leaves early (threads past the last row idle along).
+//
+// Dual walk. The two walks of a pair differ only at nodes on the swept column
+// whose threshold lies in [lo, hi), so a tree is walked with ONE cursor for
+// as long as both values take the same branch: a node on another column or a
+// one-hot node is decided once by the row, a node on the swept column is
+// decided for lo and for hi. If lo <= thr < hi the walk forks: cursor A goes
+// on with lo, cursor B with hi, and each decides every later node itself (it
+// may meet the swept column again). Cursors of one tree never meet again, so
+// "forked" is one bit per tree. ALE_ILP trees are in flight per thread (up
+// to 2 x ALE_ILP independent gather chains once forked); both leaves of each
+// are added to the two sums afterwards, in tree order.
+//
+// Bounds by construction (the note on forest_sweep_kernel): a tree whose
+// [base, base + size) does not lie inside the node table is skipped, a node
+// index is compared unsigned against the tree's node count before every load
+// (a bad one ends the cursor on a leaf of +0.0), a feature index outside the
+// table reads as a leaf, source columns are clamped, the walk loop runs at
+// most size times, and the interval search is bounded by its halving range.
+#define ALE_BLOCK 64
+#define ALE_ILP 4
+#define ALE_MAX_EDGES 128
+
+// Generated without packed f32 VALU instructions, per function (as the MMD
+// kernels are), so that every other kernel of this file keeps its code.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define ALE_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define ALE_NO_PACKED_F32
+#endif
+
+// Whether the cursor on split node `nd` goes left for the thread's staged row
+// with `swept_v` standing in the swept numeric column `col` (one-hot test or
+// numeric column, clamped); `on_swept` tells whether the node tests `col`.
+__device__ __forceinline__ bool ale_goes_left(
+    int4 nd, const int* __restrict__ feat_col, const int* __restrict__ feat_code,
+    const short* s_codes, const float* s_nums, int tid, int col, float swept_v,
+    bool& on_swept)
+{
+  const int fcol = feat_col[nd.x];
+  const int code = feat_code[nd.x];
+  on_swept = code < 0 && fcol == col;
+  const float v = (code >= 0)
+      ? ((s_codes[min((unsigned)fcol, (unsigned)(N_CAT - 1)) * ALE_BLOCK + tid] == (short)code)
+             ? 1.0f : 0.0f)
+      : (on_swept ? swept_v
+                  : s_nums[min((unsigned)fcol, (unsigned)(N_NUM - 1)) * ALE_BLOCK + tid]);
+  return v <= __int_as_float(nd.y);
+}
+
+// Node `rel` of the tree at `base` with `size` nodes; an index outside the
+// tree reads as a leaf of +0.0 and is never used to index.
+__device__ __forceinline__ int4 ale_load(
+    const int4* __restrict__ nodes, int base, unsigned size, int rel)
+{
+  return ((unsigned)rel < size) ? nodes[base + rel] : make_int4(-1, 0, 0, 0);
+}
+
+ALE_NO_PACKED_F32 __global__ __launch_bounds__(ALE_BLOCK) void forest_ale_kernel(
+    const short* __restrict__ codes,    // [R, N_CAT]
+    const float* __restrict__ nums,     // [R, N_NUM], NaNs not yet imputed
+    const float* __restrict__ medians,  // [N_NUM]
+    const int4* __restrict__ nodes,     // [n_nodes] {feat, bits, left, right}
+    const int* __restrict__ tree_off,   // [T+1]
+    int n_trees,
+    unsigned n_nodes,
+    const int* __restrict__ feat_col,   // [F]
+    const int* __restrict__ feat_code,  // [F]
+    unsigned n_feat,
+    const int* __restrict__ players,    // [E] numeric schema indices
+    const int* __restrict__ edge_off,   // [E+1]
+    const float* __restrict__ edges,    // ragged, ascending per entry
+    int n_entries,
+    int n_rows,
+    int* __restrict__ interval,         // [E, R]; every entry is written
+    double2* __restrict__ sums)         // [E, R] {S(lo), S(hi)}; all written
+{
+  __shared__ short s_codes[N_CAT * ALE_BLOCK];
+  __shared__ float s_nums[N_NUM * ALE_BLOCK];
+  __shared__ float s_edges[ALE_MAX_EDGES];
+
+  const int tid = threadIdx.x;
+  const int row = blockIdx.x * ALE_BLOCK + tid;
+  const bool live = row < n_rows;
+
+  if (live) {
+#pragma unroll
+    for (int c = 0; c < N_CAT; ++c)
+      s_codes[c * ALE_BLOCK + tid] = codes[(size_t)row * N_CAT + c];
+#pragma unroll
+    for (int c = 0; c < N_NUM; ++c) {
+      const float v = nums[(size_t)row * N_NUM + c];
+      s_nums[c * ALE_BLOCK + tid] = isnan(v) ? medians[c] : v;
+    }
+  }
+
+  const int4 dead = make_int4(-1, 0, 0, 0);  // a leaf of +0.0
+
+  for (int e = blockIdx.y; e < n_entries; e += gridDim.y) {
+    // block-uniform: the entry's column and edges
+    const int e0 = edge_off[e];
+    const int n_edge = min(max(edge_off[e + 1] - e0, 0), ALE_MAX_EDGES);
+    const int col = (int)min((unsigned)(players[e] - N_CAT), (unsigned)(N_NUM - 1));
+    __syncthreads();  // the entry before is done with s_edges
+    for (int i = tid; i < n_edge; i += ALE_BLOCK) s_edges[i] = edges[e0 + i];
+    __syncthreads();
+    if (!live || n_edge < 2) continue;  // the host refuses n_edge < 2
+
+    // k = clip(#{z < x}, 1, Ke): the first edge that is not below x
+    const float x = s_nums[col * ALE_BLOCK + tid];
+    int first = 0, last = n_edge;
+    while (first < last) {
+      const int mid = (first + last) >> 1;
+      if (s_edges[mid] < x) first = mid + 1; else last = mid;
+    }
+    const int k = min(max(first, 1), n_edge - 1);
+    const float lo = s_edges[k - 1];
+    const float hi = s_edges[k];
+
+    double sum_lo = 0.0, sum_hi = 0.0;
+    for (int t = 0; t < n_trees; t += ALE_ILP) {
+      int4 a[ALE_ILP], b[ALE_ILP];
+      int base[ALE_ILP];
+      unsigned size[ALE_ILP];
+      bool forked[ALE_ILP];
+      unsigned longest = 0;
+#pragma unroll
+      for (int s = 0; s < ALE_ILP; ++s) {
+        base[s] = 0;
+        size[s] = 0;
+        forked[s] = false;
+        a[s] = dead;
+        b[s] = dead;
+        if (t + s < n_trees) {
+          const int b0 = tree_off[t + s];
+          const int sz = tree_off[t + s + 1] - b0;
+          if (b0 >= 0 && sz > 0 && (unsigned)b0 + (unsigned)sz <= n_nodes) {
+            base[s] = b0;
+            size[s] = (unsigned)sz;
+            a[s] = nodes[b0];
+          }
+        }
+        longest = max(longest, size[s]);
+      }
+      bool any = true;
+      for (unsigned it = 0; it < longest && any; ++it) {
+        any = false;
+#pragma unroll
+        for (int s = 0; s < ALE_ILP; ++s) {
+          // cursor B first: a fork made below takes its first own step in
+          // the next round, after both loads have been issued
+          if (forked[s] && (unsigned)b[s].x < n_feat) {
+            bool on_swept;
+            const bool left = ale_goes_left(b[s], feat_col, feat_code, s_codes, s_nums, tid,
+                                            col, hi, on_swept);
+            b[s] = ale_load(nodes, base[s], size[s], left ? b[s].z : b[s].w);
+            any = true;
+          }
+          if ((unsigned)a[s].x < n_feat) {
+            bool on_swept;
+            const bool left = ale_goes_left(a[s], feat_col, feat_code, s_codes, s_nums, tid,
+                                            col, lo, on_swept);
+            if (!forked[s] && on_swept && left && !(hi <= __int_as_float(a[s].y))) {
+              forked[s] = true;  // lo <= thr < hi: hi goes right
+              b[s] = ale_load(nodes, base[s], size[s], a[s].w);
+            }
+            a[s] = ale_load(nodes, base[s], size[s], left ? a[s].z : a[s].w);
+            any = true;
+          }
+        }
+      }
+      // a cursor the loop bound stopped on a split (bad tables only) adds 0
+#pragma unroll
+      for (int s = 0; s < ALE_ILP; ++s) {
+        if (t + s < n_trees) {
+          const int4 fin = forked[s] ? b[s] : a[s];
+          sum_lo += ((unsigned)a[s].x < n_feat) ? 0.0 : (double)__int_as_float(a[s].y);
+          sum_hi += ((unsigned)fin.x < n_feat) ? 0.0 : (double)__int_as_float(fin.y);
+        }
+      }
+    }
+    const size_t at = (size_t)e * n_rows + row;
+    interval[at] = k;
+    sums[at] = make_double2(sum_lo, sum_hi);
+  }
+}
+
 // Exact single-feature sweep for counterfactuals: the raw classifier sum of
 // one row as ONE numeric column moves over the whole real line, every other
 // column held fixed. The sum is piecewise constant in that column; its
@@ -1963,6 +2164,97 @@ torch::Tensor forest_whatif(
       out.data_ptr<double>());
   HIP_CHECK(hipGetLastError());
   return out;
+}
+
+// Accumulated local effects (forest_ale_kernel): {interval i32[E, R], sums
+// f64[E, R, 2]} of the R sample rows under each of the E entries. `players`
+// (i32[E], numeric schema indices), `edge_off` (i32[E+1]) and `edges` (f32,
+// the entries' edge lists one after the other) are HOST tables; they are
+// checked here (players numeric, offsets that span `edges` with 2 to
+// ALE_MAX_EDGES edges per entry, edges finite and strictly ascending) and
+// then copied to the device on the caller's stream. Stateless like
+// forest_whatif; the kernel bounds-checks the forest tables itself.
+std::vector<torch::Tensor> forest_ale(
+    torch::Tensor codes, torch::Tensor nums,
+    torch::Tensor cls_nodes, torch::Tensor cls_off,
+    torch::Tensor feat_col, torch::Tensor feat_code,
+    torch::Tensor medians, torch::Tensor players,
+    torch::Tensor edge_off, torch::Tensor edges, int64_t block_target)
+{
+  check_inputs(codes, nums);
+  TORCH_CHECK(block_target >= 1 && block_target <= 65535, "bad block_target");
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType st, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == codes.device(), name,
+                " must be on the inputs' GPU");
+    TORCH_CHECK(t.scalar_type() == st && t.is_contiguous(), name,
+                " has the wrong dtype or is not contiguous");
+  };
+  auto on_host = [&](const torch::Tensor& t, torch::ScalarType st, const char* name) {
+    TORCH_CHECK(!t.is_cuda() && t.scalar_type() == st && t.is_contiguous() && t.dim() == 1,
+                name, " must be a contiguous one-dimensional host table of its dtype");
+  };
+  on_dev(nums, torch::kFloat32, "nums");
+  on_dev(cls_nodes, torch::kInt32, "cls_nodes");
+  on_dev(cls_off, torch::kInt32, "cls_off");
+  on_dev(feat_col, torch::kInt32, "feat_col");
+  on_dev(feat_code, torch::kInt32, "feat_code");
+  on_dev(medians, torch::kFloat32, "medians");
+  on_host(players, torch::kInt32, "players");
+  on_host(edge_off, torch::kInt32, "edge_off");
+  on_host(edges, torch::kFloat32, "edges");
+  TORCH_CHECK(cls_nodes.dim() == 2 && cls_nodes.size(1) == 4, "cls_nodes must be [n, 4]");
+  TORCH_CHECK(cls_nodes.size(0) < (int64_t(1) << 31), "too many nodes");
+  TORCH_CHECK(feat_col.numel() == feat_code.numel(), "feat_col/feat_code size mismatch");
+  TORCH_CHECK(medians.numel() == N_NUM, "medians must have N_NUM entries");
+  TORCH_CHECK(cls_off.numel() >= 2, "forest has no trees");
+
+  const int64_t E = players.numel();
+  const int64_t R = codes.size(0);
+  TORCH_CHECK(E >= 1, "forest_ale needs at least one entry");
+  TORCH_CHECK(R >= 1, "forest_ale needs at least one sample row");
+  TORCH_CHECK(E <= 65535 && R < (int64_t(1) << 31), "too many entries or rows");
+  TORCH_CHECK(edge_off.numel() == E + 1, "edge_off must have one entry more than players");
+  const int* pl = players.data_ptr<int>();
+  const int* eo = edge_off.data_ptr<int>();
+  const float* ed = edges.data_ptr<float>();
+  TORCH_CHECK(eo[0] == 0 && (int64_t)eo[E] == edges.numel(), "edge_off does not span edges");
+  for (int64_t e = 0; e < E; ++e) {
+    TORCH_CHECK(pl[e] >= N_CAT && pl[e] < N_SRC, "entry ", e,
+                ": player must be a numeric feature (categorical columns have no intervals)");
+    const int64_t n = (int64_t)eo[e + 1] - eo[e];
+    TORCH_CHECK(n >= 2 && n <= ALE_MAX_EDGES && eo[e] >= 0, "entry ", e,
+                ": edge_off must ascend by 2 to ", ALE_MAX_EDGES, " edges per entry");
+    for (int64_t i = eo[e]; i < eo[e + 1]; ++i)
+      TORCH_CHECK(std::isfinite(ed[i]) && (i == eo[e] || ed[i - 1] < ed[i]), "entry ", e,
+                  ": edges must be finite and strictly ascending");
+  }
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)codes.get_device());
+  auto dev = codes.device();
+  auto interval = torch::empty({E, R}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
+  auto sums = torch::empty({E, R, 2}, torch::TensorOptions().dtype(torch::kFloat64).device(dev));
+  auto players_dev = players.to(dev);
+  auto edge_off_dev = edge_off.to(dev);
+  auto edges_dev = edges.to(dev);
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  const int T = (int)cls_off.size(0) - 1;
+  const int row_blocks = ceil_div((int)R, ALE_BLOCK);
+  // One-wave blocks; a block takes more than one entry only once the grid
+  // passes block_target blocks (as forest_whatif).
+  const int chunks = (int)std::max<int64_t>(
+      1, std::min<int64_t>(ceil_div((int)block_target, row_blocks), E));
+  hipLaunchKernelGGL(forest_ale_kernel, dim3(row_blocks, chunks),
+      dim3(ALE_BLOCK), 0, stream,
+      codes.data_ptr<short>(), nums.data_ptr<float>(), medians.data_ptr<float>(),
+      reinterpret_cast<const int4*>(cls_nodes.data_ptr<int>()),
+      cls_off.data_ptr<int>(), T, (unsigned)cls_nodes.size(0),
+      feat_col.data_ptr<int>(), feat_code.data_ptr<int>(), (unsigned)feat_col.numel(),
+      players_dev.data_ptr<int>(), edge_off_dev.data_ptr<int>(), edges_dev.data_ptr<float>(),
+      (int)E, (int)R, interval.data_ptr<int>(),
+      reinterpret_cast<double2*>(sums.data_ptr<double>()));
+  HIP_CHECK(hipGetLastError());
+  return {interval, sums};
 }
 
 // Exact single-feature sweep (forest_sweep_kernel + forest_sweep_search_kernel)
@@ -5096,6 +5388,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cls_off"), py::arg("feat_col"), py::arg("feat_code"),
         py::arg("medians"), py::arg("jobs"), py::arg("block_target") = 8192);
   m.attr("WHATIF_ROWS_PER_BLOCK") = py::int_(WHATIF_BLOCK);
+  m.def("forest_ale", &forest_ale,
+        "Accumulated local effects: per (entry, row) the row's grid interval "
+        "and the raw forest sums at its two edges, {i32[E,R], f64[E,R,2]} "
+        "(dual walk; gfx950)",
+        py::arg("codes"), py::arg("nums"), py::arg("cls_nodes"),
+        py::arg("cls_off"), py::arg("feat_col"), py::arg("feat_code"),
+        py::arg("medians"), py::arg("players"), py::arg("edge_off"),
+        py::arg("edges"), py::arg("block_target") = 8192);
+  m.attr("ALE_ROWS_PER_BLOCK") = py::int_(ALE_BLOCK);
+  m.attr("ALE_MAX_EDGES") = py::int_(ALE_MAX_EDGES);
   m.def("forest_sweep", &forest_sweep,
         "Exact single-feature sweep: per {row, numeric column} job the raw "
         "forest sum of every threshold interval, searched on the device for "
