@@ -10,6 +10,7 @@ Replaces the reference's Databricks bundle + GitHub Actions + Bicep pipeline
     python -m creditcore pdp    --model-directory ./model --features credit_limit,age --out pdp.json
     python -m creditcore ale    --model-directory ./model --features bill_amount_3,age --out ale.json
     python -m creditcore counterfactual --model-directory ./model --data rows.csv --out cf.json
+    python -m creditcore importance --model-directory ./model --data labelled.csv --out imp.json
     python -m creditcore drift-mmd --model-directory ./model --data batch.csv [--reference ref.csv]
 """
 
@@ -376,6 +377,50 @@ def _cmd_counterfactual(argv):
                       "features": len(doc["features"]), "device": eng.device}))
 
 
+def _cmd_importance(argv):
+    """Offline model-validation artefact: permutation feature importance of a
+    packaged model on labelled CSV rows, written as JSON
+    (ScoringEngine.permutation_importance)."""
+    p = argparse.ArgumentParser(prog="creditcore importance")
+    p.add_argument("--model-directory", default="./model")
+    p.add_argument("--data", required=True,
+                   help="labelled CSV rows (the train --data schema with its "
+                        "target column); at most 65536 rows")
+    p.add_argument("--features", default=None,
+                   help="comma-separated feature names (default: all)")
+    p.add_argument("--n-repeats", type=int, default=5)
+    p.add_argument("--scoring", default="roc_auc",
+                   choices=["accuracy", "neg_log_loss", "neg_brier_score", "roc_auc"])
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--threshold", type=float, default=0.5)
+    p.add_argument("--device", default="auto")
+    p.add_argument("--out", default=None)
+    a = p.parse_args(argv)
+    import pandas as pd
+
+    from .engine import load_engine
+    from .schema import TARGET
+
+    eng = load_engine(a.model_directory, device=a.device)
+    df = pd.read_csv(a.data)
+    if TARGET not in df.columns:
+        sys.exit(f"{a.data} has no {TARGET!r} column: importance needs labels")
+    doc = eng.permutation_importance_records(
+        df, df[TARGET].to_numpy(),
+        features=[n.strip() for n in a.features.split(",")] if a.features else None,
+        n_repeats=a.n_repeats, scoring=a.scoring, seed=a.seed, threshold=a.threshold,
+    )
+    for res in doc["results"]:
+        res["importances"] = res["importances"].tolist()
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(doc, f)
+        print(json.dumps({"out": a.out, "features": len(doc["results"]),
+                          "sample_rows": doc["sample_rows"], "device": eng.device}))
+    else:
+        print(json.dumps(doc))
+
+
 def _cmd_drift_mmd(argv):
     """Offline multivariate drift test (MMD with a permutation p-value) of
     CSV rows under a packaged model (ScoringEngine.mmd_drift)."""
@@ -445,6 +490,7 @@ def main():
         "pdp": _cmd_pdp,
         "ale": _cmd_ale,
         "counterfactual": _cmd_counterfactual,
+        "importance": _cmd_importance,
         "drift-mmd": _cmd_drift_mmd,
     }
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:

@@ -191,6 +191,21 @@ class ScoringEngine:
     # profiles/bench_results/ale_micro.txt. That is the largest call the caps
     # allow (ALE_MAX_ROWS x N_NUM), so today no call is sliced.
     ALE_LAUNCH_JOBS = 917504
+    # permutation_importance: most (table row, sample row) pairs of one
+    # forest_permute launch (a table row is one permutation of one column, a
+    # pair at most one walk of the whole forest); a call above it runs as
+    # several launches over table-row slices cut at job boundaries. Sized
+    # like PDP_LAUNCH_PAIRS: the largest measured pair count whose launch on
+    # the flagship forest (RF 500 x depth 16, whole features of 5 repeats at
+    # 65,536 rows) is no longer than 1.25 x the method="shap" launch at
+    # SHAP_MAX_ROWS measured in the same run: forest_shap at 1024 rows
+    # 60.22 ms (bound 75.28 ms), forest_permute at 60 table rows x 65,536
+    # rows = 3,932,160 pairs 71.14 ms (80 table rows: 95.18 ms, over the
+    # bound) on an MI355X, bench/perm_micro.py,
+    # profiles/bench_results/perm_micro.txt. The default call at the row cap
+    # (23 features x 5 repeats and the baseline row, 7.6 M pairs) runs as two
+    # launches, the largest the caps allow (48.3 M pairs) as thirteen.
+    PERM_LAUNCH_PAIRS = 3932160
     # counterfactuals: most {row, numeric column} jobs of one forest_sweep
     # launch; a call above it runs as several launches over job slices. Held
     # against the method="shap" launch at SHAP_MAX_ROWS measured in the same
@@ -999,6 +1014,124 @@ class ScoringEngine:
 
         return run
 
+    # ---------------------------------------------- permutation importance
+    def permutation_importance(
+        self,
+        sample,
+        labels,
+        features=None,
+        n_repeats: int = 5,
+        scoring: str = "roc_auc",
+        seed: int = 0,
+        threshold: float = 0.5,
+        permutations=None,
+    ) -> dict:
+        """Permutation feature importance of the classifier on a labelled
+        sample (the estimator of sklearn.inspection.permutation_importance):
+        how much a score of the model on ``labels`` drops when ONE column of
+        the sample is shuffled among its rows, ``n_repeats`` shuffles per
+        feature (creditcore/importance.py).
+
+        ``sample`` is an encoded ``(codes, nums)`` pair of up to 65,536 rows,
+        ``labels`` one 0/1 per row. ``features`` defaults to all 23 names.
+        ``scoring`` is one of importance.SCORINGS (``threshold`` is the
+        decision cut of "accuracy"). The shuffles are drawn from
+        ``np.random.default_rng(seed)`` in (feature, repeat) order unless
+        ``permutations`` i[n_features, n_repeats, R] gives them.
+
+        Returns ``{"baseline_score", "results", "sample_rows", "scoring",
+        "n_repeats"}``; a result holds ``feature``, ``importances``
+        f64[n_repeats] (baseline minus permuted score), ``importances_mean``
+        and ``importances_std`` (ddof 0). The scoring session is not touched.
+        Caps (creditcore/importance.py) raise ExplainTooLarge."""
+        from . import importance as imp
+        from .pdp import finalize
+
+        p = self.packed
+        try:
+            names = imp.parse_features(features)
+            reps = imp.check_args(n_repeats, scoring)
+            thr = imp.check_threshold(threshold)
+            codes = np.ascontiguousarray(sample[0], dtype=np.int16)
+            nums = np.ascontiguousarray(sample[1], dtype=np.float32)
+            r = len(codes)
+            if codes.shape != (r, N_CAT) or nums.shape != (r, N_NUM):
+                raise ValueError(f"sample must be (codes [R, {N_CAT}], nums [R, {N_NUM}])")
+            if r > imp.IMPORTANCE_MAX_ROWS:
+                raise imp.ImportanceTooLarge(
+                    f"the sample is capped at {imp.IMPORTANCE_MAX_ROWS} rows (got {r})"
+                )
+            y = imp.check_labels(labels, r, scoring)
+            take = imp.permutation_source(permutations, seed, len(names), reps, r)
+        except imp.ImportanceTooLarge as e:
+            raise ExplainTooLarge(str(e)) from None
+        # Table row 0 is the identity on the first feature's column (the
+        # baseline: the same code path gives the unpermuted sums), then
+        # n_repeats rows per feature.
+        players = np.array([FEATURES.index(n) for n in names], dtype=np.int32)
+        perm_player = np.concatenate([players[:1], np.repeat(players, reps)])
+        scores = np.empty(len(perm_player), dtype=np.float64)
+        cls_kind, n_trees = int(getattr(p, "cls_kind", 0)), int(p.cls_n_trees)
+        with self._explain_lock:
+            if self.device == "cuda":
+                run = self._permute_gpu(codes, nums)
+            else:
+                nums_imp = cpu_ref.impute_nums(p, nums)
+
+                def run(pl, pm):
+                    return cpu_ref.forest_permute_cpu(p, codes, nums_imp, pl, pm)
+            for a, b in imp.launch_slices(perm_player, r, self.PERM_LAUNCH_PAIRS, imp.PERM_ILP):
+                perm = take(b - a) if a else np.concatenate(
+                    [np.arange(r, dtype=np.int32)[None, :], take(b - 1)]
+                )
+                raw = run(perm_player[a:b], np.ascontiguousarray(perm, dtype=np.int32))
+                prob = finalize(raw, cls_kind, float(p.cls_bias), n_trees, "probability")
+                scores[a:b] = [imp.score(scoring, y, row, thr) for row in prob]
+        drops = (scores[0] - scores[1:]).reshape(len(names), reps)
+        return {
+            "baseline_score": float(scores[0]),
+            "results": [
+                {
+                    "feature": n,
+                    "importances": d,
+                    "importances_mean": float(d.mean()),
+                    "importances_std": float(d.std()),
+                }
+                for n, d in zip(names, drops)
+            ],
+            "sample_rows": r,
+            "scoring": scoring,
+            "n_repeats": reps,
+        }
+
+    def _permute_gpu(self, codes: np.ndarray, nums: np.ndarray):
+        """One-launch runner of forest_permute on the device (a slice of the
+        permutation table in, numpy f64[Q, R] sums out); the caller holds
+        _explain_lock. The sample is uploaded here, once per call."""
+        import torch
+
+        ext = self._gpu["ext"]
+        dev = torch.device("cuda", self.device_index)
+        m = self._forest_dev()
+        smp = (torch.from_numpy(codes).to(dev), torch.from_numpy(nums).to(dev))
+
+        def run(perm_player: np.ndarray, perm: np.ndarray):
+            with torch.cuda.device(dev):
+                out = ext.forest_permute(
+                    smp[0],
+                    smp[1],
+                    m["cls_nodes"],
+                    m["cls_off"],
+                    m["feat_col"],
+                    m["feat_code"],
+                    m["medians"],
+                    torch.from_numpy(np.ascontiguousarray(perm_player, dtype=np.int32)),
+                    torch.from_numpy(perm),
+                )
+                return out.cpu().numpy()  # the D2H copy synchronizes
+
+        return run
+
     # ---------------------------------------------------- counterfactuals
     def counterfactuals(
         self,
@@ -1296,6 +1429,13 @@ class ScoringEngine:
         if reference is not None:
             reference = encode_batch(reference, self.packed.vocabs)
         return self.mmd_drift(codes, nums, reference=reference, **kw)
+
+    def permutation_importance_records(self, records, labels, **kw) -> dict:
+        """permutation_importance on a request body (list of dicts /
+        DataFrame) and its labels."""
+        return self.permutation_importance(
+            encode_batch(records, self.packed.vocabs), labels, **kw
+        )
 
     def counterfactual_records(self, records, **kw) -> dict:
         """counterfactuals on a request body (list of dicts / DataFrame)."""

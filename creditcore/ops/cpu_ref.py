@@ -208,6 +208,51 @@ def forest_ale_cpu(
     return interval, sums
 
 
+def forest_permute_cpu(
+    packed: PackedModel,
+    codes: np.ndarray,
+    nums_imp: np.ndarray,
+    perm_player: np.ndarray,
+    perm: np.ndarray,
+    max_pairs: int = 1 << 21,
+) -> np.ndarray:
+    """Permutation-importance raw classifier sums, f64[Q, R], the reference
+    of forest_permute_kernel: ``out[q, r]`` is the tree-order sum of row r of
+    the (imputed) sample with the column of schema player ``perm_player[q]``
+    (0..N_CAT-1 categorical, N_CAT.. numeric) taken from donor row
+    ``perm[q, r]``. Deliberately the dumb version: per table row, copy the
+    sample, replace the column by ``column[perm[q]]`` and run the scorer's
+    own traversal on the copy; table rows are only stacked into one traversal
+    call so long as it stays under ``max_pairs`` (row, tree) pairs."""
+    codes = np.ascontiguousarray(codes, dtype=np.int16)
+    nums_imp = np.ascontiguousarray(nums_imp, dtype=np.float32)
+    perm_player = np.asarray(perm_player, dtype=np.int64).reshape(-1)
+    perm = np.asarray(perm, dtype=np.int64)
+    n_q, r = len(perm_player), len(codes)
+    if n_q < 1 or r < 1:
+        raise ValueError("forest_permute needs at least one table row and one sample row")
+    if perm.shape != (n_q, r):
+        raise ValueError(f"perm must be [{n_q}, {r}]")
+    if ((perm_player < 0) | (perm_player >= N_CAT + N_NUM)).any():
+        raise ValueError("perm_player out of range")
+    if ((perm < 0) | (perm >= r)).any():
+        raise ValueError("perm holds a donor outside the sample")
+    out = np.empty((n_q, r), dtype=np.float64)
+    step = max(1, max_pairs // max(1, r * packed.cls_n_trees))
+    for a in range(0, n_q, step):
+        b = min(a + step, n_q)
+        c = np.tile(codes, (b - a, 1))
+        x = np.tile(nums_imp, (b - a, 1))
+        for k, q in enumerate(range(a, b)):
+            rows, player = slice(k * r, (k + 1) * r), perm_player[q]
+            if player < N_CAT:
+                c[rows, player] = codes[perm[q], player]
+            else:
+                x[rows, player - N_CAT] = nums_imp[perm[q], player - N_CAT]
+        out[a:b] = forest_raw_cpu(packed, c, x, tree_order=True).reshape(b - a, r)
+    return out
+
+
 def forest_sweep_cpu(
     packed: PackedModel,
     codes: np.ndarray,

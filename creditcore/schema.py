@@ -234,6 +234,46 @@ class AleOutput(BaseModel):
     results: list[AleCurve]
 
 
+class ImportanceRequest(BaseModel):
+    """POST /explain/importance request: the records as /score takes them,
+    one 0/1 label per record, the features to permute (default: all), the
+    shuffles per feature, the score (accuracy, neg_log_loss, neg_brier_score
+    or roc_auc), the seed of the shuffles and the decision threshold of
+    "accuracy"."""
+
+    records: list[dict]
+    labels: list[float]
+    features: list[str] | None = None
+    n_repeats: int = 5
+    scoring: str = "roc_auc"
+    seed: int = 0
+    threshold: float = 0.5
+
+    model_config = ConfigDict(extra="ignore")
+
+
+class FeatureImportance(BaseModel):
+    """``importances[k]`` is the baseline score minus the score with the
+    feature's column shuffled by permutation k; ``importances_std`` has
+    ddof 0."""
+
+    feature: str
+    importances: list[float]
+    importances_mean: float
+    importances_std: float
+
+
+class ImportanceOutput(BaseModel):
+    """POST /explain/importance response: one entry per requested feature,
+    in request order."""
+
+    baseline_score: float
+    scoring: str
+    n_repeats: int
+    sample_rows: int
+    results: list[FeatureImportance]
+
+
 class CounterfactualRequest(BaseModel):
     """POST /explain/counterfactual request: the records as /explain takes
     them, the features to move (default: all), the decision threshold on the

@@ -43,6 +43,8 @@ from .schema import (
     CounterfactualOutput,
     CounterfactualRequest,
     ExplainOutput,
+    ImportanceOutput,
+    ImportanceRequest,
     LoanApplicant,
     MmdDriftOutput,
     MmdDriftRequest,
@@ -825,6 +827,71 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
                 for key in ("thresholds", "probabilities"):
                     if key in entry:
                         entry[key] = entry[key].tolist()
+        metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
+        return _json_response(out)
+
+    @app.post("/explain/importance", response_model=ImportanceOutput)
+    async def explain_importance(req: ImportanceRequest):
+        """Permutation feature importance of the classifier on the posted
+        labelled records: the drop of a score of the model when one feature's
+        column is shuffled among the records
+        (ScoringEngine.permutation_importance). There is no default sample:
+        the packed background sample has no labels. One attempt on one live
+        replica; bypasses the micro-batcher."""
+        import asyncio
+
+        from .importance import IMPORTANCE_MAX_REPEATS, IMPORTANCE_MAX_ROWS
+
+        metrics: Metrics = state["metrics"]
+        engines = state["engines"]
+        pool: ReplicaPool = state["pool"]
+        if not req.records:
+            raise HTTPException(status_code=400, detail="empty request batch")
+        if len(req.records) > IMPORTANCE_MAX_ROWS:
+            raise HTTPException(
+                status_code=413,
+                detail=f"/explain/importance takes at most {IMPORTANCE_MAX_ROWS} rows",
+            )
+        if req.n_repeats > IMPORTANCE_MAX_REPEATS:
+            raise HTTPException(
+                status_code=413,
+                detail=f"/explain/importance takes at most {IMPORTANCE_MAX_REPEATS} repeats",
+            )
+        try:
+            codes, nums = encode_batch(req.records, engines[0].packed.vocabs)
+        except (ValueError, TypeError, KeyError) as e:
+            raise HTTPException(status_code=422, detail=f"bad record: {e}")
+        try:
+            idx = pool.pick()
+        except RuntimeError:
+            metrics.observe_error()
+            raise HTTPException(status_code=503, detail="no healthy replicas")
+        t0 = time.perf_counter()
+
+        def call():
+            return engines[idx].permutation_importance(
+                (codes, nums),
+                req.labels,
+                features=req.features,
+                n_repeats=req.n_repeats,
+                scoring=req.scoring,
+                seed=req.seed,
+                threshold=req.threshold,
+            )
+
+        try:
+            out = await asyncio.get_running_loop().run_in_executor(None, call)
+            pool.report_ok(idx)
+        except ExplainTooLarge as e:  # the request's fault, not the replica's
+            raise HTTPException(status_code=413, detail=str(e))
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        except Exception as e:
+            metrics.observe_error()
+            pool.report_fail(idx)
+            raise HTTPException(status_code=500, detail=f"permutation importance failed: {e}")
+        for res in out["results"]:
+            res["importances"] = res["importances"].tolist()
         metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
         return _json_response(out)
 

@@ -1237,6 +1237,183 @@ ALE_NO_PACKED_F32 __global__ __launch_bounds__(ALE_BLOCK) void forest_ale_kernel
   }
 }
 
+// Permutation importance: out[q, row] is the raw classifier sum of the row
+// with ONE source column replaced by the value another row (the donor
+// perm[q, row]) holds there. Table row q permutes schema player
+// perm_player[q] (0..N_CAT-1 a categorical column, N_CAT..N_SRC-1 a numeric).
+// A numeric donor gives its imputed value (NaN -> the median); a categorical
+// donor's code answers every one-hot test of the column. Each entry is the
+// tree-order f64 sum forest_whatif_kernel gives for that one override, bit for
+// bit; unlike a what-if job the override differs from row to row.
+//
+// Work split as forest_whatif_kernel: one thread owns a (job, row) and all
+// trees, one wave per block, rows staged column-major in LDS with fused
+// imputation (own slots only, so no barrier), blockIdx.y strides over the
+// jobs, plain stores. A job {player, q0, n} is up to PERM_ILP consecutive
+// table rows of one player (the repeats of a feature; the launcher groups
+// them). The thread reads its n donor values into registers and never writes
+// the LDS slot, so there is nothing to restore.
+//
+// Shared base walk. The n walks of a tree are identical down to the first
+// node that tests the job's column, so the thread walks the row's own values
+// ONCE to that node (or to the leaf if the path never tests the column: then
+// all n sums take that leaf and the tree has cost one walk, not n). From that
+// node n cursors go on side by side, the ILP slots that WHATIF_ILP spends on
+// trees; each decides every later node itself, with its donor value at nodes
+// of the job's column (it may be tested again further down) and the row's LDS
+// value elsewhere. Leaves are added per tree, so every sum is in tree order.
+//
+// Bounds by construction (the note on forest_ale_kernel): a tree outside the
+// node table is skipped, a node index is compared unsigned against the tree's
+// size before every load, a feature index outside the table reads as a leaf,
+// base walk and cursors together take at most `size` steps, source columns,
+// table rows and donor indices are clamped.
+#define PERM_BLOCK 64
+#define PERM_ILP 4
+
+// The staged row's own value at split node `nd` (one-hot test or numeric
+// column, clamped); `code` is the node's category code (-1: numeric) and
+// `on_player` tells whether the node tests the job's column.
+__device__ __forceinline__ float perm_own_value(
+    int4 nd, const int* __restrict__ feat_col, const int* __restrict__ feat_code,
+    const short* s_codes, const float* s_nums, int tid, bool cat_job, int pcol,
+    int& code, bool& on_player)
+{
+  const int fcol = feat_col[nd.x];
+  code = feat_code[nd.x];
+  on_player = ((code >= 0) == cat_job) && fcol == pcol;
+  return (code >= 0)
+      ? ((s_codes[min((unsigned)fcol, (unsigned)(N_CAT - 1)) * PERM_BLOCK + tid] == (short)code)
+             ? 1.0f : 0.0f)
+      : s_nums[min((unsigned)fcol, (unsigned)(N_NUM - 1)) * PERM_BLOCK + tid];
+}
+
+ALE_NO_PACKED_F32 __global__ __launch_bounds__(PERM_BLOCK) void forest_permute_kernel(
+    const short* __restrict__ codes,    // [R, N_CAT]
+    const float* __restrict__ nums,     // [R, N_NUM], NaNs not yet imputed
+    const float* __restrict__ medians,  // [N_NUM]
+    const int4* __restrict__ nodes,     // [n_nodes] {feat, bits, left, right}
+    const int* __restrict__ tree_off,   // [T+1]
+    int n_trees,
+    unsigned n_nodes,
+    const int* __restrict__ feat_col,   // [F]
+    const int* __restrict__ feat_code,  // [F]
+    unsigned n_feat,
+    const int4* __restrict__ jobs,      // [J] {player, q0, n, 0}
+    int n_jobs,
+    const int* __restrict__ perm,       // [Q, R] donor rows
+    int n_q,
+    int n_rows,
+    double* __restrict__ out)           // [Q, R]; every entry is written
+{
+  __shared__ short s_codes[N_CAT * PERM_BLOCK];
+  __shared__ float s_nums[N_NUM * PERM_BLOCK];
+
+  const int tid = threadIdx.x;
+  const int row = blockIdx.x * PERM_BLOCK + tid;
+  if (row >= n_rows) return;  // no barrier below: own LDS slots only
+
+#pragma unroll
+  for (int c = 0; c < N_CAT; ++c)
+    s_codes[c * PERM_BLOCK + tid] = codes[(size_t)row * N_CAT + c];
+#pragma unroll
+  for (int c = 0; c < N_NUM; ++c) {
+    const float v = nums[(size_t)row * N_NUM + c];
+    s_nums[c * PERM_BLOCK + tid] = isnan(v) ? medians[c] : v;
+  }
+
+  const int4 dead = make_int4(-1, 0, 0, 0);  // a leaf of +0.0
+
+  for (int j = blockIdx.y; j < n_jobs; j += gridDim.y) {
+    const int4 job = jobs[j];
+    const bool cat_job = (unsigned)job.x < (unsigned)N_CAT;
+    const int pcol = cat_job ? job.x
+                             : (int)min((unsigned)(job.x - N_CAT), (unsigned)(N_NUM - 1));
+    const int q0 = min(max(job.y, 0), n_q - 1);
+    const int n = min(max(job.z, 0), min(PERM_ILP, n_q - q0));
+
+    // the donors' values in the job's column: a category code, or the bits
+    // of the imputed f32
+    int donor_bits[PERM_ILP];
+#pragma unroll
+    for (int i = 0; i < PERM_ILP; ++i) {
+      donor_bits[i] = 0;
+      if (i < n) {
+        const size_t d = min((unsigned)perm[(size_t)(q0 + i) * n_rows + row],
+                             (unsigned)(n_rows - 1));
+        if (cat_job) {
+          donor_bits[i] = codes[d * N_CAT + pcol];
+        } else {
+          const float v = nums[d * N_NUM + pcol];
+          donor_bits[i] = __float_as_int(isnan(v) ? medians[pcol] : v);
+        }
+      }
+    }
+
+    double sum[PERM_ILP];
+#pragma unroll
+    for (int i = 0; i < PERM_ILP; ++i) sum[i] = 0.0;
+
+    for (int t = 0; t < n_trees; ++t) {
+      const int b0 = tree_off[t];
+      const int sz = tree_off[t + 1] - b0;
+      if (b0 < 0 || sz <= 0 || (unsigned)b0 + (unsigned)sz > n_nodes) continue;
+      const unsigned size = (unsigned)sz;
+
+      // the shared base walk, on the row's own values
+      int4 cur = nodes[b0];
+      bool resume = false;
+      unsigned it = 0;
+      for (; it < size && (unsigned)cur.x < n_feat; ++it) {
+        int code;
+        const float v = perm_own_value(cur, feat_col, feat_code, s_codes, s_nums, tid,
+                                       cat_job, pcol, code, resume);
+        if (resume) break;
+        cur = ale_load(nodes, b0, size, (v <= __int_as_float(cur.y)) ? cur.z : cur.w);
+      }
+
+      if (!resume) {
+        // the path never tests the column: one leaf for all repeats (a walk
+        // the loop bound stopped on a split, bad tables only, adds 0)
+        const double leaf = ((unsigned)cur.x < n_feat) ? 0.0 : (double)__int_as_float(cur.y);
+#pragma unroll
+        for (int i = 0; i < PERM_ILP; ++i) sum[i] += leaf;  // slots past n are not stored
+        continue;
+      }
+
+      // n cursors from the first node on the job's column
+      int4 c[PERM_ILP];
+#pragma unroll
+      for (int i = 0; i < PERM_ILP; ++i) c[i] = (i < n) ? cur : dead;
+      bool any = true;
+      for (; it < size && any; ++it) {
+        any = false;
+#pragma unroll
+        for (int i = 0; i < PERM_ILP; ++i) {
+          if ((unsigned)c[i].x < n_feat) {
+            int code;
+            bool on_player;
+            float v = perm_own_value(c[i], feat_col, feat_code, s_codes, s_nums, tid,
+                                     cat_job, pcol, code, on_player);
+            if (on_player)
+              v = cat_job ? (((short)donor_bits[i] == (short)code) ? 1.0f : 0.0f)
+                          : __int_as_float(donor_bits[i]);
+            c[i] = ale_load(nodes, b0, size, (v <= __int_as_float(c[i].y)) ? c[i].z : c[i].w);
+            any = true;
+          }
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < PERM_ILP; ++i)
+        sum[i] += ((unsigned)c[i].x < n_feat) ? 0.0 : (double)__int_as_float(c[i].y);
+    }
+
+#pragma unroll
+    for (int i = 0; i < PERM_ILP; ++i)
+      if (i < n) out[(size_t)(q0 + i) * n_rows + row] = sum[i];
+  }
+}
+
 // Exact single-feature sweep for counterfactuals: the raw classifier sum of
 // one row as ONE numeric column moves over the whole real line, every other
 // column held fixed. The sum is piecewise constant in that column; its
@@ -2255,6 +2432,101 @@ std::vector<torch::Tensor> forest_ale(
       reinterpret_cast<double2*>(sums.data_ptr<double>()));
   HIP_CHECK(hipGetLastError());
   return {interval, sums};
+}
+
+// Permutation importance (forest_permute_kernel): f64[Q, R], the raw
+// classifier sum of each of the R sample rows with column perm_player[q]
+// taken from donor row perm[q, r]. `perm_player` (i32[Q], schema players,
+// equal players adjacent) and `perm` (i32[Q, R]) are HOST tables; they are
+// checked here (players in [0, N_SRC), every donor in [0, R)), consecutive
+// table rows of one player are grouped into jobs of up to PERM_ILP, and
+// both are copied to the device on the caller's stream. Stateless like
+// forest_ale; the kernel bounds-checks the forest tables itself.
+torch::Tensor forest_permute(
+    torch::Tensor codes, torch::Tensor nums,
+    torch::Tensor cls_nodes, torch::Tensor cls_off,
+    torch::Tensor feat_col, torch::Tensor feat_code,
+    torch::Tensor medians, torch::Tensor perm_player,
+    torch::Tensor perm, int64_t block_target)
+{
+  check_inputs(codes, nums);
+  TORCH_CHECK(block_target >= 1 && block_target <= 65535, "bad block_target");
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType st, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == codes.device(), name,
+                " must be on the inputs' GPU");
+    TORCH_CHECK(t.scalar_type() == st && t.is_contiguous(), name,
+                " has the wrong dtype or is not contiguous");
+  };
+  auto on_host = [&](const torch::Tensor& t, int64_t dim, const char* name) {
+    TORCH_CHECK(!t.is_cuda() && t.scalar_type() == torch::kInt32 && t.is_contiguous() &&
+                t.dim() == dim, name, " must be a contiguous ", dim,
+                "-dimensional host int32 table");
+  };
+  on_dev(nums, torch::kFloat32, "nums");
+  on_dev(cls_nodes, torch::kInt32, "cls_nodes");
+  on_dev(cls_off, torch::kInt32, "cls_off");
+  on_dev(feat_col, torch::kInt32, "feat_col");
+  on_dev(feat_code, torch::kInt32, "feat_code");
+  on_dev(medians, torch::kFloat32, "medians");
+  on_host(perm_player, 1, "perm_player");
+  on_host(perm, 2, "perm");
+  TORCH_CHECK(cls_nodes.dim() == 2 && cls_nodes.size(1) == 4, "cls_nodes must be [n, 4]");
+  TORCH_CHECK(cls_nodes.size(0) < (int64_t(1) << 31), "too many nodes");
+  TORCH_CHECK(feat_col.numel() == feat_code.numel(), "feat_col/feat_code size mismatch");
+  TORCH_CHECK(medians.numel() == N_NUM, "medians must have N_NUM entries");
+  TORCH_CHECK(cls_off.numel() >= 2, "forest has no trees");
+
+  const int64_t Q = perm_player.numel();
+  const int64_t R = codes.size(0);
+  TORCH_CHECK(Q >= 1, "forest_permute needs at least one perm_player entry");
+  TORCH_CHECK(R >= 1, "forest_permute needs at least one sample row");
+  TORCH_CHECK(Q < (int64_t(1) << 31) && R < (int64_t(1) << 31), "too many table or sample rows");
+  TORCH_CHECK(perm.size(0) == Q && perm.size(1) == R, "perm must be [", Q, ", ", R,
+              "] (one row per perm_player entry, one donor per sample row), got [",
+              perm.size(0), ", ", perm.size(1), "]");
+  const int* pl = perm_player.data_ptr<int>();
+  const int* pm = perm.data_ptr<int>();
+  for (int64_t q = 0; q < Q; ++q) {
+    TORCH_CHECK(pl[q] >= 0 && pl[q] < N_SRC, "perm_player[", q, "] = ", pl[q],
+                " is outside [0, ", N_SRC, ")");
+    bool ok = true;
+    for (int64_t r = 0; r < R; ++r) ok &= (unsigned)pm[q * R + r] < (unsigned)R;
+    TORCH_CHECK(ok, "perm row ", q, " holds a donor outside [0, ", R, ")");
+  }
+
+  // jobs {player, q0, n, 0}: runs of one player, cut every PERM_ILP rows
+  std::vector<int> jb;
+  for (int64_t q = 0; q < Q;) {
+    int64_t n = 1;
+    while (n < PERM_ILP && q + n < Q && pl[q + n] == pl[q]) ++n;
+    jb.insert(jb.end(), {pl[q], (int)q, (int)n, 0});
+    q += n;
+  }
+  const int64_t J = (int64_t)jb.size() / 4;
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)codes.get_device());
+  auto dev = codes.device();
+  auto out = torch::empty({Q, R}, torch::TensorOptions().dtype(torch::kFloat64).device(dev));
+  auto jobs_dev = torch::from_blob(jb.data(), {J, 4}, torch::kInt32).to(dev);
+  auto perm_dev = perm.to(dev);
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  const int T = (int)cls_off.size(0) - 1;
+  const int row_blocks = ceil_div((int)R, PERM_BLOCK);
+  // One-wave blocks; a block takes more than one job only once the grid
+  // passes block_target blocks (as forest_whatif).
+  const int chunks = (int)std::max<int64_t>(
+      1, std::min<int64_t>(ceil_div((int)block_target, row_blocks), J));
+  hipLaunchKernelGGL(forest_permute_kernel, dim3(row_blocks, chunks),
+      dim3(PERM_BLOCK), 0, stream,
+      codes.data_ptr<short>(), nums.data_ptr<float>(), medians.data_ptr<float>(),
+      reinterpret_cast<const int4*>(cls_nodes.data_ptr<int>()),
+      cls_off.data_ptr<int>(), T, (unsigned)cls_nodes.size(0),
+      feat_col.data_ptr<int>(), feat_code.data_ptr<int>(), (unsigned)feat_col.numel(),
+      reinterpret_cast<const int4*>(jobs_dev.data_ptr<int>()), (int)J,
+      perm_dev.data_ptr<int>(), (int)Q, (int)R, out.data_ptr<double>());
+  HIP_CHECK(hipGetLastError());
+  return out;
 }
 
 // Exact single-feature sweep (forest_sweep_kernel + forest_sweep_search_kernel)
@@ -5398,6 +5670,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("edges"), py::arg("block_target") = 8192);
   m.attr("ALE_ROWS_PER_BLOCK") = py::int_(ALE_BLOCK);
   m.attr("ALE_MAX_EDGES") = py::int_(ALE_MAX_EDGES);
+  m.def("forest_permute", &forest_permute,
+        "Permutation importance: per (table row, sample row) the raw forest "
+        "sum of the row with one column taken from its donor row, f64[Q,R] "
+        "(shared base walk, the repeats of a feature side by side; gfx950)",
+        py::arg("codes"), py::arg("nums"), py::arg("cls_nodes"),
+        py::arg("cls_off"), py::arg("feat_col"), py::arg("feat_code"),
+        py::arg("medians"), py::arg("perm_player"), py::arg("perm"),
+        py::arg("block_target") = 8192);
+  m.attr("PERM_ROWS_PER_BLOCK") = py::int_(PERM_BLOCK);
+  m.attr("PERM_ILP") = py::int_(PERM_ILP);
   m.def("forest_sweep", &forest_sweep,
         "Exact single-feature sweep: per {row, numeric column} job the raw "
         "forest sum of every threshold interval, searched on the device for "
