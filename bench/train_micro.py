@@ -4,6 +4,7 @@
     python bench/train_micro.py --rows 1000000 --skip-exact-gbt
     python bench/train_micro.py --mode forest --rows 20000 --depth 8
     python bench/train_micro.py --rows 20000 --monotone 3 --skip-exact-gbt
+    python bench/train_micro.py --mode forest --deep --rows 1000000 [--dense-levels 10]
 
 Every estimator gets the same preprocessed matrix (the pipeline's
 [one-hot | 14 numerics] feature space, dense f32), the same 80/20 split and
@@ -19,7 +20,10 @@ unconstrained ones.
 ``--mode forest`` times HistForestClassifier (hrf; host binning, bootstrap
 draws and transfers included) against sklearn RandomForestClassifier on
 ``--sklearn-jobs`` threads at equal n_estimators / max_depth / max_features,
-and reports the held-out log-loss and ROC-AUC of both.
+and reports the held-out log-loss and ROC-AUC of both. ``--deep`` makes it
+the deep shape: depth 16 with ``deep_trees=True`` (segmented levels past
+``--dense-levels``, default the class's 12); ``--skip-sklearn`` leaves the
+sklearn fit out when only the hrf time of another setting is wanted.
 """
 
 from __future__ import annotations
@@ -62,10 +66,15 @@ def _forest(a, xtr, xte, ytr, yte, shape) -> None:
     common = {"n_estimators": a.trees, "max_depth": a.depth,
               "max_features": a.max_features, "random_state": a.seed}
     ours = f"hrf[{a.device}]"
+    if a.dense_levels is not None:
+        HistForestClassifier._dense_levels = a.dense_levels
     makers = {
-        ours: (lambda: HistForestClassifier(**common, device=a.device), a.repeats),
+        ours: (lambda: HistForestClassifier(**common, device=a.device, deep_trees=a.deep),
+               a.repeats),
         "sklearn_rf": (lambda: RandomForestClassifier(**common, n_jobs=a.sklearn_jobs), 1),
     }
+    if a.skip_sklearn:
+        del makers["sklearn_rf"]
     results = {}
     for name, (make, repeats) in makers.items():
         fits = []
@@ -83,10 +92,12 @@ def _forest(a, xtr, xte, ytr, yte, shape) -> None:
     print(json.dumps({
         "event": "summary", **shape, "max_features": a.max_features,
         "sklearn_jobs": a.sklearn_jobs,
+        **({"deep_trees": True,
+            "dense_levels": HistForestClassifier._dense_levels} if a.deep else {}),
         **{f"{k}_{m}": v[m] for k, v in results.items()
            for m in ("fit_s", "log_loss", "roc_auc")},
-        "speedup_vs_sklearn_rf": round(
-            results["sklearn_rf"]["fit_s"] / results[ours]["fit_s"], 2),
+        **({} if a.skip_sklearn else {"speedup_vs_sklearn_rf": round(
+            results["sklearn_rf"]["fit_s"] / results[ours]["fit_s"], 2)}),
     }), flush=True)
 
 
@@ -98,6 +109,13 @@ def main(argv=None) -> None:
                     help="forest mode: 'sqrt', an integer or 'none'")
     ap.add_argument("--sklearn-jobs", type=int, default=16,
                     help="forest mode: threads of sklearn's RandomForestClassifier")
+    ap.add_argument("--deep", action="store_true",
+                    help="forest mode: depth 16 with deep_trees=True")
+    ap.add_argument("--dense-levels", type=int, default=None,
+                    help="forest mode with --deep: levels that keep the dense "
+                         "histogram (HistForestClassifier._dense_levels)")
+    ap.add_argument("--skip-sklearn", action="store_true",
+                    help="forest mode: time hrf only")
     ap.add_argument("--rows", type=int, default=20_000)
     ap.add_argument("--trees", type=int, default=100)
     ap.add_argument("--depth", type=int, default=6)
@@ -111,6 +129,10 @@ def main(argv=None) -> None:
                     help="gbt mode: also fit hgbt with the first N numeric "
                          "columns constrained, signs alternating from +1")
     a = ap.parse_args(argv)
+    if a.deep:
+        if a.mode != "forest":
+            ap.error("--deep needs --mode forest")
+        a.depth = 16
 
     from sklearn.model_selection import train_test_split
 

@@ -64,6 +64,9 @@ def _cmd_train(argv):
                    help="monotone constraints for --algorithm hgbt over numeric "
                         "features: +1 = the score never falls as the feature "
                         "rises, -1 = never rises (credit_limit=-1,age=+1)")
+    p.add_argument("--deep-trees", action="store_true",
+                   help="--algorithm hrf: keep search depths up to 24 instead "
+                        "of clamping them to 12 (segmented deep levels)")
     p.add_argument("--data", default=None,
                    help="CSV with the UCI schema (the reference's curated "
                         "table, 00-create-external-table.ipynb); synthetic "
@@ -71,6 +74,8 @@ def _cmd_train(argv):
     a = p.parse_args(argv)
     if a.monotone and a.algorithm != "hgbt":
         p.error("--monotone needs --algorithm hgbt")
+    if a.deep_trees and a.algorithm != "hrf":
+        p.error("--deep-trees needs --algorithm hrf")
     from .train import train_and_register
 
     df = None
@@ -91,6 +96,7 @@ def _cmd_train(argv):
         min_roc_auc=a.min_roc_auc,
         train_device=a.train_device,
         monotone=a.monotone,
+        deep_trees=a.deep_trees,
     )
     print(uri)
 

@@ -64,7 +64,7 @@ def make_classifier_pipeline(params: dict, algorithm: str = "rf") -> Pipeline:
     carry ``device`` for the training device), "hrf"
     (models.hrf.HistForestClassifier — the random forest trained by HIP
     kernels, many trees per launch, packed and scored like "rf"; takes
-    ``device`` too), or "et"
+    ``device`` too, and ``deep_trees=True`` for depths up to 24), or "et"
     (ExtraTreesClassifier — identical tree structure and leaf-fraction-mean
     semantics to RF, so it rides the RF pack/score path unchanged).
     """
@@ -92,12 +92,13 @@ def make_classifier_pipeline(params: dict, algorithm: str = "rf") -> Pipeline:
             params["monotone_cst"] = monotone_columns(monotone)
         estimator = HistGBTClassifier(**params)
     elif algorithm == "hrf":
-        from .hrf import MAX_DEPTH, HistForestClassifier
+        from .hrf import MAX_DEPTH, MAX_DEPTH_DEEP, HistForestClassifier
 
         params = dict(params)
         params.pop("criterion", None)  # Gini only (models/hrf.py)
         if "max_depth" in params:  # the search space draws up to 24
-            params["max_depth"] = min(int(params["max_depth"]), MAX_DEPTH)
+            limit = MAX_DEPTH_DEEP if params.get("deep_trees") else MAX_DEPTH
+            params["max_depth"] = min(int(params["max_depth"]), limit)
         estimator = HistForestClassifier(**params)
     elif algorithm == "et":
         from sklearn.ensemble import ExtraTreesClassifier

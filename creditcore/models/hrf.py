@@ -39,9 +39,20 @@ devices are specified to build byte-identical forests:
   cover is W. A child stays open while W >= 2*min_samples_leaf, 0 < P < W
   and depth remains.
 
-Limits: binary targets, ``max_depth <= 12``, ``max_bins <= 256``, at most
-1024 features (the split kernel's per-feature tables live in LDS), no OOB
-score, no class weights, no missing-value direction (the pipeline imputes).
+Deep trees (``deep_trees=True``, ``max_depth <= 24``): a level's dense
+histogram is i64[K, 2, total_bins], which past level 12 is gigabytes of
+zeros, because a deep slot holds a handful of rows. In a fit deeper than 12
+the levels from ``_dense_levels`` on therefore run *segmented*: the open rows are bucketed by
+slot and each slot's histogram lives only in LDS while its split is chosen
+(hrf_seg_*_kernel; the CPU backend builds the same dense histogram in slot
+chunks). The forest is the one the three primitives above define, whichever
+levels run segmented.
+
+Limits: binary targets, ``max_depth <= 12`` (24 with ``deep_trees``),
+``max_bins <= 256``, at most 1024 features (the split kernel's per-feature
+tables live in LDS), fewer than 2^31 / 255 rows with ``deep_trees`` (int32
+LDS sums), no OOB score, no class weights, no missing-value direction (the
+pipeline imputes).
 
 The fitted state is plain numpy, as in models/hgbt.py, and
 ``pack.pack_classifier_pipeline`` packs it as a leaf-mean forest
@@ -66,10 +77,12 @@ from .hgbt import (
     plan_feature_groups,
 )
 
+MAX_DEPTH_DEEP = 24  # with deep_trees=True; levels past _dense_levels run segmented
 MAX_FEATURES = 1024  # hrf_split_kernel's LDS tables (ext.HRF_MAX_FEATS)
 # level histogram of one tree batch, worst case; it sets the batch size
 HIST_BUDGET_BYTES = 1 << 30
 _CPU_SPLIT_CHUNK = 256  # slots per hrf_split_cpu call (bounds its temporaries)
+_CPU_SEG_HIST_BYTES = 1 << 28  # histogram of one slot chunk of a segmented CPU level
 
 
 def bootstrap_weights(random_state, tree: int, n_rows: int, bootstrap: bool = True) -> np.ndarray:
@@ -132,6 +145,23 @@ class _CpuBackend:
             for a in range(0, len(hist), step)
         ])
 
+    def seg_split(self, node, slot_off, slot_meta, max_open, m, min_leaf, seed) -> np.ndarray:
+        """A segmented level: hist and split over chunks of the level's slots,
+        so that no more than _CPU_SEG_HIST_BYTES of histogram exist at once.
+        A chunk [a, b) of the flat slot list sees tree t's rows at their slot
+        minus the tree's first slot in the chunk; rows of other chunks fall
+        outside [0, k) and hrf_hist_cpu leaves them out."""
+        k, total = int(slot_off[-1]), int(self.bin_off[-1])
+        step = max(1, _CPU_SEG_HIST_BYTES // (16 * total))
+        out = []
+        for a in range(0, k, step):
+            b = min(a + step, k)
+            first = np.maximum(a - slot_off[:-1], 0).astype(np.int32)
+            sub_off = (np.clip(slot_off, a, b) - a).astype(np.int32)
+            hist = self.hist(node - first[:, None], sub_off, 0)
+            out.append(self.split(hist, slot_meta[a:b], m, min_leaf, seed))
+        return np.concatenate(out)
+
     def route(self, node, table, slot_off):
         return self._ref.hrf_route_cpu(self.bins, table, node, slot_off)
 
@@ -152,6 +182,7 @@ class _GpuBackend:
         self.rows_per_block = int(ext.HRF_MAX_ROWS_PER_BLOCK)
         self.lds_bytes = LDS_BUDGET_BYTES
         self._groups: dict = {}
+        self._bins_rm = None
 
     def _dev(self, a: np.ndarray):
         return self._torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
@@ -190,6 +221,20 @@ class _GpuBackend:
             hist, self.bin_off, self._dev(slot_meta), m, min_leaf, seed
         ).cpu().numpy()
 
+    def seg_split(self, node, slot_off, slot_meta, max_open, m, min_leaf, seed) -> np.ndarray:
+        """A segmented level: the open rows bucketed by slot, then one fused
+        histogram-and-split block per slot; no level histogram exists."""
+        if self._bins_rm is None:  # u8[N, F]: a row's bins in one read
+            self._bins_rm = self.bins.t().contiguous()
+        self._slot_off = self._dev(slot_off)
+        seg_off, rows = self._ext.hrf_seg_build(
+            self.bins, self.y, self.w, node, self._slot_off, int(slot_off[-1]), max_open
+        )
+        seed = seed - (1 << 64) if seed >= (1 << 63) else seed
+        return self._ext.hrf_seg_split(
+            rows, seg_off, self._bins_rm, self.bin_off, self._dev(slot_meta), m, min_leaf, seed
+        ).cpu().numpy()
+
     def route(self, node, table, slot_off):
         self._ext.hrf_route(self.bins, self._dev(table), node, self._slot_off)
         return node
@@ -210,22 +255,25 @@ def grow_forest_batch(
     max_features: int,
     min_leaf: int,
     seed: int,
+    dense_levels: int = MAX_DEPTH,
 ) -> list[dict]:
     """Grow the trees ``tree_ids`` (global indices) together, level by level,
     from their row weights ``w`` u8[TB, N] and the targets ``y`` u8[N].
 
     A level is a flat list of open slots, sorted by tree and, within a tree,
     by node id; a node's id is its place in the tree's breadth-first creation
-    order, so it does not depend on which trees share the batch. Returns one
+    order, so it does not depend on which trees share the batch. Levels from
+    ``dense_levels`` on run segmented (``backend.seg_split``). Returns one
     dict of sklearn-style flat arrays per tree (hgbt.grow_tree's layout)."""
     tb = len(tree_ids)
-    cap = 2 ** (max_depth + 1) - 1
-    cl = np.full((tb, cap), -1, dtype=np.int32)
-    cr = np.full((tb, cap), -1, dtype=np.int32)
-    feature = np.full((tb, cap), -2, dtype=np.int32)
-    threshold = np.full((tb, cap), -2.0, dtype=np.float32)
-    value = np.zeros((tb, cap), dtype=np.float32)
-    cover = np.zeros((tb, cap), dtype=np.int64)
+    fills = (-1, -1, -2, -2.0, 0, 0)
+    dtypes = (np.int32, np.int32, np.int32, np.float32, np.float32, np.int64)
+    # node arrays [tb, cap] double as the trees grow; 2^(max_depth+1) entries
+    # per tree would be 33 M at depth 24
+    cap = min(2 ** (max_depth + 1) - 1, 4095)
+    cl, cr, feature, threshold, value, cover = (
+        np.full((tb, cap), fill, dtype=dt) for fill, dt in zip(fills, dtypes)
+    )
     n_used = np.ones(tb, dtype=np.int64)
 
     def is_open(p_sum, w_sum, depth):
@@ -250,8 +298,14 @@ def grow_forest_batch(
         per_tree = np.bincount(st, minlength=tb)
         slot_off = np.concatenate([[0], np.cumsum(per_tree)]).astype(np.int32)
         slot_meta = np.stack([tree_ids[st], sn], axis=1).astype(np.int32)
-        hist = backend.hist(node, slot_off, int(per_tree.max()))
-        rec = backend.split(hist, slot_meta, max_features, min_leaf, seed)
+        if depth < dense_levels:
+            hist = backend.hist(node, slot_off, int(per_tree.max()))
+            rec = backend.split(hist, slot_meta, max_features, min_leaf, seed)
+        else:  # a row weighs at least 1: the slots' cover bounds the open rows
+            rec = backend.seg_split(
+                node, slot_off, slot_meta, int(cover[st, sn].sum()),
+                max_features, min_leaf, seed,
+            )
         feat, bin_ = rec[:, 1], rec[:, 2]
         p_l, w_l, p_t, w_t = rec[:, 3], rec[:, 4], rec[:, 5], rec[:, 6]
         split = feat >= 0
@@ -266,6 +320,14 @@ def grow_forest_batch(
         n_split = np.bincount(pt, minlength=tb)
         left = n_used[pt] + 2 * (np.arange(len(pt)) - _excl_cumsum(n_split)[pt])
         n_used += 2 * n_split
+        if n_used.max() > cap:
+            cap = int(max(2 * cap, n_used.max()))
+            cl, cr, feature, threshold, value, cover = (
+                np.concatenate(
+                    [arr, np.full((tb, cap - arr.shape[1]), fill, dtype=arr.dtype)], axis=1
+                )
+                for arr, fill in zip((cl, cr, feature, threshold, value, cover), fills)
+            )
         cl[pt, parent], cr[pt, parent] = left, left + 1
         feature[pt, parent] = feat[split]
         threshold[pt, parent] = bin_threshold[bin_off[feat[split]] + bin_[split]]
@@ -302,6 +364,9 @@ class HistForestClassifier(ClassifierMixin, BaseEstimator):
     and no extension it raises ``ExtensionMissing`` and never falls back."""
 
     _tree_batch = None  # trees per batch; None: from HIST_BUDGET_BYTES
+    # a fit deeper than MAX_DEPTH runs its levels from this depth on segmented;
+    # 8 was the fastest of 8 / 10 / 12 at 16k and 800k rows (docs/design.md)
+    _dense_levels = 8
 
     def __init__(
         self,
@@ -313,6 +378,7 @@ class HistForestClassifier(ClassifierMixin, BaseEstimator):
         max_bins=MAX_BINS,
         random_state=None,
         device="auto",
+        deep_trees=False,
     ):
         self.n_estimators = n_estimators
         self.max_depth = max_depth
@@ -322,11 +388,13 @@ class HistForestClassifier(ClassifierMixin, BaseEstimator):
         self.max_bins = max_bins
         self.random_state = random_state
         self.device = device
+        self.deep_trees = deep_trees
 
     # -- training ----------------------------------------------------------
     def _check_params(self):
-        if not 1 <= int(self.max_depth) <= MAX_DEPTH:
-            raise ValueError(f"max_depth must be in [1, {MAX_DEPTH}]")
+        limit = MAX_DEPTH_DEEP if self.deep_trees else MAX_DEPTH
+        if not 1 <= int(self.max_depth) <= limit:
+            raise ValueError(f"max_depth must be in [1, {limit}]")
         if not 2 <= int(self.max_bins) <= MAX_BINS:
             raise ValueError(f"max_bins must be in [2, {MAX_BINS}]")
         if int(self.n_estimators) < 1:
@@ -358,6 +426,11 @@ class HistForestClassifier(ClassifierMixin, BaseEstimator):
         n_rows, n_feat = x.shape
         if n_feat > MAX_FEATURES:
             raise ValueError(f"HistForestClassifier takes at most {MAX_FEATURES} features")
+        if self.deep_trees and n_rows * 255 >= 2**31:
+            raise ValueError(
+                f"deep_trees=True takes fewer than {2**31 // 255 + 1} rows: a slot's "
+                "int32 bin sums could overflow"
+            )
         m = resolve_max_features(self.max_features, n_feat)
         if not np.isfinite(x).all():
             raise ValueError("HistForestClassifier needs finite features (impute first)")
@@ -388,9 +461,14 @@ class HistForestClassifier(ClassifierMixin, BaseEstimator):
         n_trees = int(self.n_estimators)
         depth, min_leaf = int(self.max_depth), int(self.min_samples_leaf)
         seed = 0 if self.random_state is None else int(self.random_state)
+        # segmented levels hold O(open rows + slots): only the dense ones count
+        deep = bool(self.deep_trees) and depth > MAX_DEPTH
+        dense = min(depth, int(self._dense_levels)) if deep else depth
         tb = self._tree_batch or tree_batch_size(
-            n_trees, n_rows, int(bin_off[-1]), depth, min_leaf
+            n_trees, n_rows, int(bin_off[-1]), max(dense, 1), min_leaf
         )
+        if self.deep_trees:  # hrf_seg_build indexes a batch's open rows in int32
+            tb = min(int(tb), max(1, (2**31 - 1) // n_rows))
         trees = []
         for t0 in range(0, n_trees, int(tb)):
             ids = np.arange(t0, min(t0 + int(tb), n_trees), dtype=np.int64)
@@ -398,7 +476,7 @@ class HistForestClassifier(ClassifierMixin, BaseEstimator):
                 [bootstrap_weights(seed, t, n_rows, bool(self.bootstrap)) for t in ids]
             )
             trees += grow_forest_batch(
-                backend, ids, w, y01, bin_off, bin_thr, depth, m, min_leaf, seed
+                backend, ids, w, y01, bin_off, bin_thr, depth, m, min_leaf, seed, dense
             )
 
         sizes = [len(t["feature"]) for t in trees]

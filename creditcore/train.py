@@ -63,22 +63,29 @@ class EvalRun:
 
 
 def _family_params(
-    params: dict, algorithm: str, train_device: str, monotone: dict | None = None
+    params: dict, algorithm: str, train_device: str, monotone: dict | None = None,
+    deep_trees: bool = False,
 ) -> dict:
     """Map a draw from the reference search space onto the estimator family:
     hgbt and hrf have no split criterion choice (hrf is Gini only), cap
     max_depth and take a training device; hgbt alone takes ``monotone``
-    ({numeric feature name: sign}, models/forest.py)."""
+    ({numeric feature name: sign}, models/forest.py) and hrf alone
+    ``deep_trees``, which lifts its cap to ``hrf.MAX_DEPTH_DEEP``."""
     if monotone and algorithm != "hgbt":
         raise ValueError("monotone constraints need algorithm 'hgbt'")
+    if deep_trees and algorithm != "hrf":
+        raise ValueError("deep_trees needs algorithm 'hrf'")
     if algorithm not in ("hgbt", "hrf"):
         return params
     from .models.hgbt import MAX_DEPTH  # models/hrf.py shares the limit
+    from .models.hrf import MAX_DEPTH_DEEP
 
     out = {k: v for k, v in params.items() if k != "criterion"}
     if "max_depth" in out:
-        out["max_depth"] = min(int(out["max_depth"]), MAX_DEPTH)
+        out["max_depth"] = min(int(out["max_depth"]), MAX_DEPTH_DEEP if deep_trees else MAX_DEPTH)
     out["device"] = train_device
+    if deep_trees:
+        out["deep_trees"] = True
     if monotone:
         out["monotone"] = {str(k): int(v) for k, v in monotone.items()}
     return out
@@ -91,6 +98,7 @@ def _evaluate(
     algorithm: str = "rf",
     train_device: str = "auto",
     monotone: dict | None = None,
+    deep_trees: bool = False,
 ) -> EvalRun:
     """One hyperparameter evaluation (reference cell-7, minus the dead
     double-fits)."""
@@ -100,7 +108,7 @@ def _evaluate(
     x_train, y_train = df_train[FEATURES], df_train[TARGET]
     x_test, y_test = df_test[FEATURES], df_test[TARGET]
 
-    fit_params = _family_params(params, algorithm, train_device, monotone)
+    fit_params = _family_params(params, algorithm, train_device, monotone, deep_trees)
     estimator = make_classifier_pipeline({**fit_params, "random_state": seed}, algorithm)
     estimator.fit(x_train, y_train.values.ravel())
     y_pred = estimator.predict(x_test)
@@ -126,6 +134,7 @@ def train_model(
     algorithm: str = "rf",
     train_device: str = "auto",
     monotone: dict | None = None,
+    deep_trees: bool = False,
 ) -> EvalRun:
     """Hyperparameter search with a real TPE sampler (reference cell-8:
     hyperopt fmin(tpe.suggest, max_evals=10); hyperopt itself is
@@ -142,7 +151,7 @@ def train_model(
         params = sampler.suggest()
         run = _evaluate(
             params, df, seed=seed, algorithm=algorithm, train_device=train_device,
-            monotone=monotone,
+            monotone=monotone, deep_trees=deep_trees,
         )
         # hyperopt minimizes; the notebook returns -roc_auc as the loss
         sampler.observe(params, -run.metrics["validation_roc_auc_score"])
@@ -214,20 +223,25 @@ def train_and_register(
     train_device: str = "auto",
     monotone: dict | None = None,
     runs_dir: str | None = None,
+    deep_trees: bool = False,
 ) -> str:
     """The full train -> package -> register job (the reference's 2-task
     Databricks DAG, train_register_model.yml:10-39). Returns the model URI
     (or the model dir when register=False). ``monotone`` ({numeric feature
     name: -1 | +1}, hgbt only) constrains every evaluated model; the best one
     is checked with ``verify_monotone`` before it is saved. ``runs_dir`` keeps
-    one ``run.json`` per evaluation (``train_model``)."""
+    one ``run.json`` per evaluation (``train_model``). ``deep_trees`` (hrf
+    only) lets the search keep depths up to 24 (models/hrf.py)."""
     if monotone and algorithm != "hgbt":
         raise ValueError("monotone constraints need algorithm 'hgbt'")
+    if deep_trees and algorithm != "hrf":
+        raise ValueError("deep_trees needs algorithm 'hrf'")
     if df is None:
         df = make_uci_shaped_frame(n_rows=n_rows, seed=seed)
     best = train_model(
         df=df, max_evals=max_evals, seed=seed, algorithm=algorithm,
         train_device=train_device, monotone=monotone, runs_dir=runs_dir,
+        deep_trees=deep_trees,
     )
     if min_roc_auc is not None:
         auc = best.metrics["validation_roc_auc_score"]

@@ -3458,12 +3458,134 @@ __device__ __forceinline__ bool hrf_better(const HrfPick& a, const HrfPick& b) {
   return a.rank < b.rank;
 }
 
-// One block per open slot. Phase 1 (hgbt_split_kernel's scan): each wavefront
-// takes every 4th feature, a lane owns 4 bins, and the feature's best valid
-// split (highest proxy, lowest bin) goes to the LDS table. Phase 2: feature
-// keys, ranks by (key, f), r* = lowest rank with a valid split, and among the
-// ranks below max(max_features, r* + 1) the highest proxy, ties to the lower
-// rank.
+// LDS tables of one slot's split choice, one entry per feature (bin -1: the
+// feature has no valid split). hrf_split_kernel and hrf_seg_split_kernel fill
+// them in phase 1 and hand them to hrf_pick_split.
+struct HrfTables {
+  double* proxy;
+  unsigned long long* key;
+  long long *pl, *wl;
+  int *bin, *rank;
+  long long* tot;  // [2]: the slot's P and W
+  int* r_star;
+  HrfPick* wave_pick;  // [HGBT_BLOCK / 64]
+};
+
+// Phase 1 for one feature, by one wavefront (hgbt_split_kernel's scan): hp /
+// hw are the feature's nb bins of the two planes, a lane owns 4 of them, and
+// the feature's best valid split (highest proxy, lowest bin) goes to the
+// tables. nb <= 0 records "no valid split". T is the histogram's word: i64
+// in global memory (hrf_split_kernel) or i32 in LDS (hrf_seg_split_kernel).
+template <typename T>
+__device__ __forceinline__ void hrf_scan_feature(
+    const T* hp, const T* hw, int nb, int f, int lane, long long min_leaf,
+    const HrfTables& t)
+{
+  double bp = 0.0;
+  int bb = -1;
+  long long bpl = 0, bwl = 0;
+  if (nb > 0) {
+    long long pp[4], pw[4];
+    long long sp = 0, sw = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int b = lane * 4 + j;
+      if (b < nb) { sp += hp[b]; sw += hw[b]; }
+      pp[j] = sp; pw[j] = sw;
+    }
+    long long ip = sp, iw = sw;  // inclusive scan of the lane totals
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const long long tp = __shfl_up(ip, d), tw = __shfl_up(iw, d);
+      if (lane >= d) { ip += tp; iw += tw; }
+    }
+    const long long P = __shfl(ip, 63), W = __shfl(iw, 63);
+    // every feature sees every open row once: feature 0's totals are the slot's
+    if (f == 0 && lane == 0) { t.tot[0] = P; t.tot[1] = W; }
+    const long long op = ip - sp, ow = iw - sw;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int b = lane * 4 + j;
+      if (b >= nb) continue;
+      const long long WL = ow + pw[j], PL = op + pp[j];
+      if (WL < min_leaf || W - WL < min_leaf) continue;
+      const double px = hrf_proxy(PL, WL, P, W);
+      if (!(px > 0.0)) continue;
+      if (bb < 0 || px > bp) { bp = px; bb = b; bpl = PL; bwl = WL; }  // ascending b
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const double op_ = __shfl_xor(bp, m);
+      const int ob = __shfl_xor(bb, m);
+      const long long opl = __shfl_xor(bpl, m), owl = __shfl_xor(bwl, m);
+      const bool take = ob >= 0 && (bb < 0 || op_ > bp || (op_ == bp && ob < bb));
+      if (take) { bp = op_; bb = ob; bpl = opl; bwl = owl; }
+    }
+  }
+  if (lane == 0) { t.proxy[f] = bp; t.bin[f] = bb; t.pl[f] = bpl; t.wl[f] = bwl; }
+}
+
+// Phase 2, by the whole block once every feature's entry is written (it
+// starts with the barrier that makes them visible): feature keys, ranks by
+// (key, f), r* = lowest rank with a valid split, and among the ranks below
+// max(max_features, r* + 1) the highest proxy, ties to the lower rank. Thread
+// 0 writes the slot's record. *t.r_star must hold n_feat on entry.
+__device__ __forceinline__ void hrf_pick_split(
+    const HrfTables& t, int n_feat, int max_features, unsigned long long seed,
+    int tree, int node_id, long long* __restrict__ o)
+{
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  for (int f = tid; f < n_feat; f += HGBT_BLOCK) t.key[f] = hrf_key(seed, tree, node_id, f);
+  __syncthreads();
+
+  for (int f = tid; f < n_feat; f += HGBT_BLOCK) {
+    const unsigned long long kf = t.key[f];
+    int rank = 0;
+    for (int g = 0; g < n_feat; ++g) {  // same g across the wave: LDS broadcast
+      const unsigned long long kg = t.key[g];
+      rank += (kg < kf || (kg == kf && g < f)) ? 1 : 0;
+    }
+    t.rank[f] = rank;
+    if (t.bin[f] >= 0) atomicMin(t.r_star, rank);
+  }
+  __syncthreads();
+
+  const int limit = max(max_features, *t.r_star + 1);
+  HrfPick best;
+  best.proxy = 0.0; best.rank = -1; best.feat = -1;
+  for (int f = tid; f < n_feat; f += HGBT_BLOCK) {
+    if (t.bin[f] < 0 || t.rank[f] >= limit) continue;
+    HrfPick c;
+    c.proxy = t.proxy[f]; c.rank = t.rank[f]; c.feat = f;
+    if (hrf_better(c, best)) best = c;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    HrfPick o2;
+    o2.proxy = __shfl_xor(best.proxy, m);
+    o2.rank = __shfl_xor(best.rank, m);
+    o2.feat = __shfl_xor(best.feat, m);
+    if (hrf_better(o2, best)) best = o2;
+  }
+  if (lane == 0) t.wave_pick[wave] = best;
+  __syncthreads();
+  if (tid == 0) {
+    for (int wv = 1; wv < HGBT_BLOCK / 64; ++wv)
+      if (hrf_better(t.wave_pick[wv], best)) best = t.wave_pick[wv];
+    const bool ok = best.rank >= 0;
+    o[0] = __double_as_longlong(ok ? best.proxy : 0.0);
+    o[1] = ok ? best.feat : -1;
+    o[2] = ok ? t.bin[best.feat] : 0;
+    o[3] = ok ? t.pl[best.feat] : 0;
+    o[4] = ok ? t.wl[best.feat] : 0;
+    o[5] = t.tot[0]; o[6] = t.tot[1];
+  }
+}
+
+// One block per open slot over the level's dense histogram. Phase 1: each
+// wavefront takes every 4th feature (hrf_scan_feature); phase 2:
+// hrf_pick_split.
 __global__ __launch_bounds__(HGBT_BLOCK) void hrf_split_kernel(
     const long long* __restrict__ hist, const int* __restrict__ bin_off,
     const int* __restrict__ slot_meta, int n_feat, int total_bins,
@@ -3473,11 +3595,12 @@ __global__ __launch_bounds__(HGBT_BLOCK) void hrf_split_kernel(
   __shared__ double f_proxy[HRF_MAX_FEATS];
   __shared__ unsigned long long f_key[HRF_MAX_FEATS];
   __shared__ long long f_pl[HRF_MAX_FEATS], f_wl[HRF_MAX_FEATS];
-  __shared__ int f_bin[HRF_MAX_FEATS];  // -1: the feature has no valid split
+  __shared__ int f_bin[HRF_MAX_FEATS];
   __shared__ int f_rank[HRF_MAX_FEATS];
   __shared__ long long tot[2];
   __shared__ int r_star;
   __shared__ HrfPick wave_pick[HGBT_BLOCK / 64];
+  const HrfTables t = {f_proxy, f_key, f_pl, f_wl, f_bin, f_rank, tot, &r_star, wave_pick};
   const int k = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -3489,96 +3612,11 @@ __global__ __launch_bounds__(HGBT_BLOCK) void hrf_split_kernel(
   for (int f = wave; f < n_feat; f += HGBT_BLOCK / 64) {
     const int fb = bin_off[f];
     const int nb = bin_off[f + 1] - fb;
-    double bp = 0.0;
-    int bb = -1;
-    long long bpl = 0, bwl = 0;
-    if (!(fb < 0 || nb <= 0 || nb > HGBT_MAX_BINS || fb + nb > total_bins)) {
-      long long pp[4], pw[4];
-      long long sp = 0, sw = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int b = lane * 4 + j;
-        if (b < nb) { sp += hp[fb + b]; sw += hw[fb + b]; }
-        pp[j] = sp; pw[j] = sw;
-      }
-      long long ip = sp, iw = sw;  // inclusive scan of the lane totals
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const long long tp = __shfl_up(ip, d), tw = __shfl_up(iw, d);
-        if (lane >= d) { ip += tp; iw += tw; }
-      }
-      const long long P = __shfl(ip, 63), W = __shfl(iw, 63);
-      // every feature sees every open row once: feature 0's totals are the slot's
-      if (f == 0 && lane == 0) { tot[0] = P; tot[1] = W; }
-      const long long op = ip - sp, ow = iw - sw;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int b = lane * 4 + j;
-        if (b >= nb) continue;
-        const long long WL = ow + pw[j], PL = op + pp[j];
-        if (WL < min_leaf || W - WL < min_leaf) continue;
-        const double px = hrf_proxy(PL, WL, P, W);
-        if (!(px > 0.0)) continue;
-        if (bb < 0 || px > bp) { bp = px; bb = b; bpl = PL; bwl = WL; }  // ascending b
-      }
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) {
-        const double op_ = __shfl_xor(bp, m);
-        const int ob = __shfl_xor(bb, m);
-        const long long opl = __shfl_xor(bpl, m), owl = __shfl_xor(bwl, m);
-        const bool take = ob >= 0 && (bb < 0 || op_ > bp || (op_ == bp && ob < bb));
-        if (take) { bp = op_; bb = ob; bpl = opl; bwl = owl; }
-      }
-    }
-    if (lane == 0) { f_proxy[f] = bp; f_bin[f] = bb; f_pl[f] = bpl; f_wl[f] = bwl; }
+    const bool ok = !(fb < 0 || nb <= 0 || nb > HGBT_MAX_BINS || fb + nb > total_bins);
+    hrf_scan_feature(ok ? hp + fb : hp, ok ? hw + fb : hw, ok ? nb : 0, f, lane, min_leaf, t);
   }
-  const int tree = slot_meta[2 * k], node_id = slot_meta[2 * k + 1];
-  for (int f = tid; f < n_feat; f += HGBT_BLOCK) f_key[f] = hrf_key(seed, tree, node_id, f);
-  __syncthreads();
-
-  for (int f = tid; f < n_feat; f += HGBT_BLOCK) {
-    const unsigned long long kf = f_key[f];
-    int rank = 0;
-    for (int g = 0; g < n_feat; ++g) {  // same g across the wave: LDS broadcast
-      const unsigned long long kg = f_key[g];
-      rank += (kg < kf || (kg == kf && g < f)) ? 1 : 0;
-    }
-    f_rank[f] = rank;
-    if (f_bin[f] >= 0) atomicMin(&r_star, rank);
-  }
-  __syncthreads();
-
-  const int limit = max(max_features, r_star + 1);
-  HrfPick best;
-  best.proxy = 0.0; best.rank = -1; best.feat = -1;
-  for (int f = tid; f < n_feat; f += HGBT_BLOCK) {
-    if (f_bin[f] < 0 || f_rank[f] >= limit) continue;
-    HrfPick c;
-    c.proxy = f_proxy[f]; c.rank = f_rank[f]; c.feat = f;
-    if (hrf_better(c, best)) best = c;
-  }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    HrfPick o;
-    o.proxy = __shfl_xor(best.proxy, m);
-    o.rank = __shfl_xor(best.rank, m);
-    o.feat = __shfl_xor(best.feat, m);
-    if (hrf_better(o, best)) best = o;
-  }
-  if (lane == 0) wave_pick[wave] = best;
-  __syncthreads();
-  if (tid == 0) {
-    for (int wv = 1; wv < HGBT_BLOCK / 64; ++wv)
-      if (hrf_better(wave_pick[wv], best)) best = wave_pick[wv];
-    long long* o = out + (size_t)k * HRF_REC;
-    const bool ok = best.rank >= 0;
-    o[0] = __double_as_longlong(ok ? best.proxy : 0.0);
-    o[1] = ok ? best.feat : -1;
-    o[2] = ok ? f_bin[best.feat] : 0;
-    o[3] = ok ? f_pl[best.feat] : 0;
-    o[4] = ok ? f_wl[best.feat] : 0;
-    o[5] = tot[0]; o[6] = tot[1];
-  }
+  hrf_pick_split(t, n_feat, max_features, seed, slot_meta[2 * k], slot_meta[2 * k + 1],
+                 out + (size_t)k * HRF_REC);
 }
 
 // grid = (row blocks, tree). hgbt_route_kernel's table protocol with the
@@ -3605,6 +3643,186 @@ __global__ __launch_bounds__(HGBT_BLOCK) void hrf_route_kernel(
     const int b = bins[(size_t)e.x * (size_t)n_rows + (size_t)r];
     tnode[r] = (b <= e.y) ? e.z : e.w;
   }
+}
+
+// ---------------------------------------------------------------------------
+// Segmented levels (HistForestClassifier(deep_trees=True), levels from
+// _dense_levels on). A deep level has many slots of a few rows each, so its
+// dense histogram would be gigabytes of zeros. Instead the level's open rows
+// are bucketed by slot,
+//
+//   hrf_seg_count_kernel    rows per slot            -> cnt i32[K]
+//   hrf_seg_scan_kernel     exclusive scan           -> seg_off i32[K+1]
+//   hrf_seg_scatter_kernel  per-slot atomic cursors  -> rows int2[open rows]
+//
+// and hrf_seg_split_kernel builds each slot's histogram in LDS, one feature
+// per wavefront at a time, and scans it on the spot: memory is O(open rows +
+// K). A rows entry is {row id, w | y << 8}; the order inside a segment is
+// whatever the atomics gave, which cannot show in a record because every sum
+// is an integer. The records equal hrf_split_kernel's over hrf_hist_kernel's
+// histogram bit for bit.
+// ---------------------------------------------------------------------------
+
+#define HRF_SEG_CHUNK 512    // rows of a slot staged in LDS per pass
+#define HRF_SCAN_BLOCK 1024  // hrf_seg_scan_kernel's only block
+
+// Flat slot of row r of tree t, or -1: in a leaf, weight 0, or bad offsets.
+__device__ __forceinline__ int hrf_open_slot(
+    const int* __restrict__ slot_off, const int* __restrict__ node,
+    const uint8_t* __restrict__ w, long long n_rows, int n_slots, int t, long long r)
+{
+  const int s0 = slot_off[t];
+  const int k = slot_off[t + 1] - s0;
+  if (s0 < 0 || k <= 0 || (long long)s0 + k > n_slots) return -1;
+  const size_t at = (size_t)t * (size_t)n_rows + (size_t)r;
+  const int nd = node[at];
+  if (nd < 0 || nd >= k || w[at] == 0) return -1;
+  return s0 + nd;
+}
+
+// grid = (row blocks, tree). cnt must be zero on entry.
+__global__ __launch_bounds__(HGBT_BLOCK) void hrf_seg_count_kernel(
+    const uint8_t* __restrict__ w, const int* __restrict__ node,
+    const int* __restrict__ slot_off, long long n_rows, int n_slots,
+    int* __restrict__ cnt)
+{
+  const long long r = (long long)blockIdx.x * HGBT_BLOCK + threadIdx.x;
+  if (r >= n_rows) return;
+  const int s = hrf_open_slot(slot_off, node, w, n_rows, n_slots, blockIdx.y, r);
+  if (s >= 0) atomicAdd(cnt + s, 1);
+}
+
+// One block: seg_off[i] = sum of cnt[0..i), seg_off[n_slots] = the total. The
+// block walks cnt in HRF_SCAN_BLOCK pieces and carries the running total.
+__global__ __launch_bounds__(HRF_SCAN_BLOCK) void hrf_seg_scan_kernel(
+    const int* __restrict__ cnt, int n_slots, int* __restrict__ seg_off)
+{
+  __shared__ int wave_sum[HRF_SCAN_BLOCK / 64];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  int carry = 0;
+  for (int base = 0; base < n_slots; base += HRF_SCAN_BLOCK) {
+    const int i = base + tid;
+    const int v = i < n_slots ? cnt[i] : 0;
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(inc, d);
+      if (lane >= d) inc += o;
+    }
+    if (lane == 63) wave_sum[wave] = inc;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int j = 0; j < HRF_SCAN_BLOCK / 64; ++j) {
+      const int ws = wave_sum[j];
+      if (j < wave) before += ws;
+      total += ws;
+    }
+    if (i < n_slots) seg_off[i] = carry + before + inc - v;
+    carry += total;
+    __syncthreads();  // wave_sum is rewritten by the next piece
+  }
+  if (tid == 0) seg_off[n_slots] = carry;
+}
+
+// grid = (row blocks, tree). cursor must be zero on entry. A row that does
+// not fit its segment or the rows array (contents changed since the count,
+// or max_open too small) is dropped, never written out of range.
+__global__ __launch_bounds__(HGBT_BLOCK) void hrf_seg_scatter_kernel(
+    const uint8_t* __restrict__ w, const uint8_t* __restrict__ y,
+    const int* __restrict__ node, const int* __restrict__ slot_off,
+    const int* __restrict__ seg_off, long long n_rows, int n_slots, int max_open,
+    int* __restrict__ cursor, int2* __restrict__ rows)
+{
+  const long long r = (long long)blockIdx.x * HGBT_BLOCK + threadIdx.x;
+  if (r >= n_rows) return;
+  const int t = blockIdx.y;
+  const int s = hrf_open_slot(slot_off, node, w, n_rows, n_slots, t, r);
+  if (s < 0) return;
+  const int a = seg_off[s];
+  const int len = seg_off[s + 1] - a;
+  const int pos = atomicAdd(cursor + s, 1);
+  if (a < 0 || pos >= len || (long long)a + pos >= max_open) return;
+  const int wt = w[(size_t)t * (size_t)n_rows + (size_t)r];
+  rows[a + pos] = make_int2((int)r, wt | (y[r] ? 256 : 0));
+}
+
+// One block per open slot; dynamic LDS = 40 B per feature (the HrfTables
+// entries). Wavefront v takes features v, v + 4, ...: per feature it zeroes
+// its private 2-plane i32 histogram (2 KB of LDS), adds the slot's rows to it
+// and runs hrf_scan_feature over it; hrf_pick_split ends the block. The rows
+// pass through LDS in pieces of HRF_SEG_CHUNK, so a slot of any length works;
+// a slot that fits one piece (nearly all of a deep level) is staged once, a
+// longer one is staged again for every round of 4 features. bins_rm is the
+// row-major u8[N, F] copy of the bins: the 4 wavefronts read neighbouring
+// bytes of the same row, and later rounds find the row's line in cache. An
+// i32 bin sum is at most rows * 255 < 2^31: the wrapper refuses N * 255 >=
+// 2^31.
+__global__ __launch_bounds__(HGBT_BLOCK) void hrf_seg_split_kernel(
+    const int2* __restrict__ rows, const int* __restrict__ seg_off,
+    const uint8_t* __restrict__ bins_rm, const int* __restrict__ bin_off,
+    const int* __restrict__ slot_meta, long long n_rows, int n_feat,
+    int max_open, int max_features, long long min_leaf,
+    unsigned long long seed, long long* __restrict__ out)
+{
+  extern __shared__ long long hrf_seg_lds[];
+  __shared__ int2 stage[HRF_SEG_CHUNK];
+  __shared__ int wave_hist[HGBT_BLOCK / 64][2 * HGBT_MAX_BINS];
+  __shared__ long long tot[2];
+  __shared__ int r_star;
+  __shared__ HrfPick wave_pick[HGBT_BLOCK / 64];
+  const int k = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  if (n_feat > HRF_MAX_FEATS) return;  // the wrapper refuses this too
+  const int a = seg_off[k];
+  const int len = seg_off[k + 1] - a;
+  if (a < 0 || len < 0 || (long long)a + len > max_open) return;
+  int* f_bin = reinterpret_cast<int*>(hrf_seg_lds + 4 * n_feat);
+  const HrfTables t = {
+      reinterpret_cast<double*>(hrf_seg_lds),
+      reinterpret_cast<unsigned long long*>(hrf_seg_lds + n_feat),
+      hrf_seg_lds + 2 * n_feat, hrf_seg_lds + 3 * n_feat,
+      f_bin, f_bin + n_feat, tot, &r_star, wave_pick};
+
+  if (tid == 0) { r_star = n_feat; tot[0] = tot[1] = 0; }
+  const int n_chunks = (len + HRF_SEG_CHUNK - 1) / HRF_SEG_CHUNK;
+  int* hp = wave_hist[wave];
+  int* hw = hp + HGBT_MAX_BINS;
+  for (int f0 = 0; f0 < n_feat; f0 += HGBT_BLOCK / 64) {
+    const int f = f0 + wave;
+    int nb = 0;
+    if (f < n_feat) {
+      nb = bin_off[f + 1] - bin_off[f];  // only the width is used here
+      if (nb <= 0 || nb > HGBT_MAX_BINS) nb = 0;
+    }
+    for (int i = lane; i < 2 * HGBT_MAX_BINS; i += 64) hp[i] = 0;
+    for (int c = 0; c < n_chunks; ++c) {
+      const int c0 = c * HRF_SEG_CHUNK;
+      const int cn = min(HRF_SEG_CHUNK, len - c0);
+      if (n_chunks > 1 || f0 == 0) {
+        __syncthreads();  // the piece staged before has been read
+        for (int i = tid; i < cn; i += HGBT_BLOCK) stage[i] = rows[a + c0 + i];
+      }
+      __syncthreads();
+      if (nb > 0) {
+        for (int i = lane; i < cn; i += 64) {
+          const int2 e = stage[i];
+          if (e.x < 0 || e.x >= n_rows) continue;
+          const int b = bins_rm[(size_t)e.x * (size_t)n_feat + (size_t)f];
+          if (b >= nb) continue;
+          const int wt = e.y & 255;
+          if (e.y & 256) atomicAdd(hp + b, wt);
+          atomicAdd(hw + b, wt);
+        }
+      }
+    }
+    __syncthreads();  // the wavefront's histogram is complete and visible
+    if (f < n_feat) hrf_scan_feature(hp, hw, nb, f, lane, min_leaf, t);
+  }
+  hrf_pick_split(t, n_feat, max_features, seed, slot_meta[2 * k], slot_meta[2 * k + 1],
+                 out + (size_t)k * HRF_REC);
 }
 
 // Shared argument checks of the three hrf wrappers: returns TB.
@@ -3734,6 +3952,96 @@ void hrf_route(torch::Tensor bins, torch::Tensor table, torch::Tensor node,
       slot_off.data_ptr<int>(), (long long)N, (int)bins.size(0), (int)K,
       node.data_ptr<int>());
   HIP_CHECK(hipGetLastError());
+}
+
+// Bucket the open rows of a level by slot: {seg_off i32[n_slots+1], rows
+// i32[max_open, 2]}; slot s owns rows[seg_off[s] : seg_off[s+1]], entries
+// {row id, w | y << 8}. max_open bounds the open rows from above (the host
+// passes the open slots' weight, and a row weighs at least 1); entries past
+// seg_off[n_slots] stay unwritten. n_slots must equal slot_off[TB].
+std::vector<torch::Tensor> hrf_seg_build(
+    torch::Tensor bins, torch::Tensor y, torch::Tensor w, torch::Tensor node,
+    torch::Tensor slot_off, int64_t n_slots, int64_t max_open)
+{
+  const int64_t TB = hrf_check_batch(bins, node, slot_off, n_slots);
+  const int64_t N = bins.size(1);
+  hgbt_check(y, bins, torch::kUInt8, "y");
+  hgbt_check(w, bins, torch::kUInt8, "w");
+  TORCH_CHECK(y.numel() == N, "y must have one entry per row");
+  TORCH_CHECK(w.dim() == 2 && w.size(0) == TB && w.size(1) == N, "w must be u8[TB, N]");
+  TORCH_CHECK(N * 255 < (int64_t(1) << 31),
+              "too many rows for the int32 sums of the segmented level");
+  TORCH_CHECK(n_slots < (int64_t(1) << 31) - 1, "too many slots");
+  TORCH_CHECK(max_open >= 0 && max_open < (int64_t(1) << 31), "max_open out of range");
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)bins.get_device());
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(bins.device());
+  auto seg_off = torch::zeros({n_slots + 1}, i32);
+  auto rows = torch::empty({max_open, 2}, i32);
+  if (N == 0 || n_slots == 0) return {seg_off, rows};
+  auto work = torch::zeros({2, n_slots}, i32);  // counts, then the cursors
+  int* cnt = work.data_ptr<int>();
+  int* cursor = cnt + n_slots;
+  const int64_t blocks = (N + HGBT_BLOCK - 1) / HGBT_BLOCK;
+  const dim3 grid((unsigned)blocks, (unsigned)TB);
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(hrf_seg_count_kernel, grid, dim3(HGBT_BLOCK), 0, stream,
+      w.data_ptr<uint8_t>(), node.data_ptr<int>(), slot_off.data_ptr<int>(),
+      (long long)N, (int)n_slots, cnt);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(hrf_seg_scan_kernel, dim3(1), dim3(HRF_SCAN_BLOCK), 0, stream,
+      cnt, (int)n_slots, seg_off.data_ptr<int>());
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(hrf_seg_scatter_kernel, grid, dim3(HGBT_BLOCK), 0, stream,
+      w.data_ptr<uint8_t>(), y.data_ptr<uint8_t>(), node.data_ptr<int>(),
+      slot_off.data_ptr<int>(), seg_off.data_ptr<int>(), (long long)N, (int)n_slots,
+      (int)max_open, cursor, reinterpret_cast<int2*>(rows.data_ptr<int>()));
+  HIP_CHECK(hipGetLastError());
+  return {seg_off, rows};
+}
+
+// Chosen split per open slot from the bucketed rows of hrf_seg_build:
+// hrf_split's i64[n_slots, HRF_REC] records without a level histogram.
+// bins_rm is the row-major u8[N, F] copy of the bins.
+torch::Tensor hrf_seg_split(torch::Tensor rows, torch::Tensor seg_off,
+                            torch::Tensor bins_rm, torch::Tensor bin_off,
+                            torch::Tensor slot_meta, int64_t max_features,
+                            int64_t min_leaf, int64_t seed)
+{
+  TORCH_CHECK(bins_rm.is_cuda() && bins_rm.scalar_type() == torch::kUInt8 &&
+              bins_rm.dim() == 2 && bins_rm.is_contiguous(),
+              "bins_rm must be a contiguous u8[N, F] GPU tensor");
+  hgbt_check(rows, bins_rm, torch::kInt32, "rows");
+  hgbt_check(seg_off, bins_rm, torch::kInt32, "seg_off");
+  hgbt_check(bin_off, bins_rm, torch::kInt32, "bin_off");
+  hgbt_check(slot_meta, bins_rm, torch::kInt32, "slot_meta");
+  const int64_t N = bins_rm.size(0), F = bins_rm.size(1);
+  const int64_t K = seg_off.numel() - 1;
+  TORCH_CHECK(F >= 1 && F <= HRF_MAX_FEATS, "feature count out of range (1..",
+              HRF_MAX_FEATS, ")");
+  TORCH_CHECK(N * 255 < (int64_t(1) << 31),
+              "too many rows for the int32 sums of the segmented level");
+  TORCH_CHECK(rows.dim() == 2 && rows.size(1) == 2, "rows must be i32[max_open, 2]");
+  TORCH_CHECK(seg_off.dim() == 1 && K >= 0, "seg_off must be i32[n_slots+1]");
+  TORCH_CHECK(bin_off.dim() == 1 && bin_off.size(0) == F + 1, "bin_off must be i32[F+1]");
+  TORCH_CHECK(slot_meta.dim() == 2 && slot_meta.size(0) == K && slot_meta.size(1) == 2,
+              "slot_meta must be i32[n_slots, 2]");
+  TORCH_CHECK(max_features >= 1 && max_features <= F, "max_features must be in [1, F]");
+  TORCH_CHECK(min_leaf >= 1, "min_leaf must be >= 1");
+  c10::hip::HIPGuard guard((c10::DeviceIndex)bins_rm.get_device());
+  auto out = torch::zeros({K, HRF_REC},
+      torch::TensorOptions().dtype(torch::kInt64).device(bins_rm.device()));
+  if (K == 0) return out;
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(hrf_seg_split_kernel, dim3((unsigned)K), dim3(HGBT_BLOCK),
+      (size_t)F * 40, stream,
+      reinterpret_cast<const int2*>(rows.data_ptr<int>()), seg_off.data_ptr<int>(),
+      bins_rm.data_ptr<uint8_t>(), bin_off.data_ptr<int>(), slot_meta.data_ptr<int>(),
+      (long long)N, (int)F, (int)rows.size(0),
+      (int)max_features, (long long)min_leaf, (unsigned long long)seed,
+      reinterpret_cast<long long*>(out.data_ptr<int64_t>()));
+  HIP_CHECK(hipGetLastError());
+  return out;
 }
 
 torch::Tensor forest_ilp_bench(
@@ -5728,6 +6036,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hrf_route", &hrf_route,
         "HistForest: move the rows of every tree of the batch, in place (gfx950)",
         py::arg("bins"), py::arg("table"), py::arg("node"), py::arg("slot_off"));
+  m.def("hrf_seg_build", &hrf_seg_build,
+        "HistForest segmented level: open rows bucketed by slot -> {seg_off, rows}",
+        py::arg("bins"), py::arg("y"), py::arg("w"), py::arg("node"),
+        py::arg("slot_off"), py::arg("n_slots"), py::arg("max_open"));
+  m.def("hrf_seg_split", &hrf_seg_split,
+        "HistForest segmented level: split record per open slot -> i64[n_slots, 7]",
+        py::arg("rows"), py::arg("seg_off"), py::arg("bins_rm"), py::arg("bin_off"),
+        py::arg("slot_meta"), py::arg("max_features"), py::arg("min_leaf"),
+        py::arg("seed"));
+  m.attr("HRF_SEG_CHUNK") = py::int_(HRF_SEG_CHUNK);
   m.attr("HRF_MAX_ROWS_PER_BLOCK") = py::int_(HRF_MAX_ROWS_PER_BLOCK);
   m.attr("HRF_MAX_FEATS") = py::int_(HRF_MAX_FEATS);
   m.def("drift_stats", &drift_stats,
