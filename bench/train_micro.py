@@ -24,6 +24,12 @@ and reports the held-out log-loss and ROC-AUC of both. ``--deep`` makes it
 the deep shape: depth 16 with ``deep_trees=True`` (segmented levels past
 ``--dense-levels``, default the class's 12); ``--skip-sklearn`` leaves the
 sklearn fit out when only the hrf time of another setting is wanted.
+
+``--bin-device {auto,cpu,cuda}`` is the trainers' ``bin_device``. On a GPU a
+first line reports the stand-alone time of host binning (bin_features) and of
+device binning (bin_features_gpu, upload included, ending in a synchronise) on
+the training matrix, best of ``--repeats`` after a warm-up; every hgbt / hrf
+record carries ``bin_s``, the binning share of its fastest fit.
 """
 
 from __future__ import annotations
@@ -57,6 +63,27 @@ def _log_loss(y, p) -> float:
     return float(-np.mean(y * np.log(p) + (1 - y) * np.log(1 - p)))
 
 
+def _bin_line(a, xtr) -> None:
+    """Stand-alone binning times of the training matrix, host and device."""
+    import torch
+
+    from creditcore.models import hgbt
+
+    if a.device != "cuda" or not torch.cuda.is_available():
+        return
+    times = {}
+    for where in ("cpu", "cuda"):
+        hgbt.bin_for_fit(xtr[:4096], 256, where)  # warm-up: code objects, allocator
+        fits = []
+        for _ in range(max(1, a.repeats)):
+            hgbt.bin_for_fit(xtr, 256, where)
+            fits.append(hgbt.last_bin_seconds)
+        times[where] = round(min(fits), 4)
+    print(json.dumps({"event": "binning", "train_rows": len(xtr), "features": xtr.shape[1],
+                      "host_bin_s": times["cpu"], "device_bin_s": times["cuda"],
+                      "bin_launch_rows": int(hgbt.BIN_LAUNCH_ROWS)}), flush=True)
+
+
 def _forest(a, xtr, xte, ytr, yte, shape) -> None:
     from sklearn.ensemble import RandomForestClassifier
     from sklearn.metrics import roc_auc_score
@@ -69,23 +96,30 @@ def _forest(a, xtr, xte, ytr, yte, shape) -> None:
     if a.dense_levels is not None:
         HistForestClassifier._dense_levels = a.dense_levels
     makers = {
-        ours: (lambda: HistForestClassifier(**common, device=a.device, deep_trees=a.deep),
+        ours: (lambda: HistForestClassifier(**common, device=a.device, deep_trees=a.deep,
+                                            bin_device=a.bin_device),
                a.repeats),
         "sklearn_rf": (lambda: RandomForestClassifier(**common, n_jobs=a.sklearn_jobs), 1),
     }
     if a.skip_sklearn:
         del makers["sklearn_rf"]
     results = {}
+    from creditcore.models import hgbt
+
     for name, (make, repeats) in makers.items():
-        fits = []
+        fits, bin_s = [], []
         for _ in range(repeats):
             est = make()
             t = time.perf_counter()
             est.fit(xtr, ytr)
             fits.append(time.perf_counter() - t)
+            bin_s.append(hgbt.last_bin_seconds)
         p = est.predict_proba(xte)[:, 1]
         results[name] = {"estimator": name, "fit_s": round(min(fits), 4),
                          "fit_s_all": [round(f, 4) for f in fits],
+                         **({"bin_device": a.bin_device,
+                             "bin_s": round(bin_s[int(np.argmin(fits))], 4)}
+                            if name == ours else {}),
                          "log_loss": round(_log_loss(yte, p), 6),
                          "roc_auc": round(float(roc_auc_score(yte, p)), 6)}
         print(json.dumps(results[name]), flush=True)
@@ -122,6 +156,8 @@ def main(argv=None) -> None:
     ap.add_argument("--learning-rate", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
+    ap.add_argument("--bin-device", default="auto", choices=["auto", "cpu", "cuda"],
+                    help="where hgbt / hrf bin their features (bin_device)")
     ap.add_argument("--repeats", type=int, default=2,
                     help="hgbt fits; the first also pays one-time GPU start-up")
     ap.add_argument("--skip-exact-gbt", action="store_true")
@@ -146,6 +182,7 @@ def main(argv=None) -> None:
     print(json.dumps({"event": "data", **shape,
                       "prep_s": round(time.perf_counter() - t0, 3)}), flush=True)
 
+    _bin_line(a, xtr)
     if a.mode == "forest":
         mf = a.max_features.lower()
         a.max_features = None if mf == "none" else mf if mf == "sqrt" else int(mf)
@@ -156,21 +193,28 @@ def main(argv=None) -> None:
               "learning_rate": a.learning_rate}
     results = {}
 
+    from creditcore.models import hgbt
+
     def run(name, make, repeats=1):
-        fits = []
+        fits, bin_s = [], []
         for _ in range(repeats):
             est = make()
             t = time.perf_counter()
             est.fit(xtr, ytr)
             fits.append(time.perf_counter() - t)
+            bin_s.append(hgbt.last_bin_seconds)
         rec = {"estimator": name, "fit_s": round(min(fits), 4),
                "fit_s_all": [round(f, 4) for f in fits],
+               **({"bin_device": a.bin_device,
+                   "bin_s": round(bin_s[int(np.argmin(fits))], 4)}
+                  if name.startswith("hgbt") else {}),
                "log_loss": round(_log_loss(yte, est.predict_proba(xte)[:, 1]), 6)}
         results[name] = rec
         print(json.dumps(rec), flush=True)
 
     run(f"hgbt[{a.device}]",
-        lambda: HistGBTClassifier(**common, device=a.device), repeats=a.repeats)
+        lambda: HistGBTClassifier(**common, device=a.device, bin_device=a.bin_device),
+        repeats=a.repeats)
     if a.monotone:
         from creditcore.schema import NUMERIC_FEATURES
 
@@ -179,7 +223,8 @@ def main(argv=None) -> None:
             ap.error(f"--monotone takes 1..{n_num}")
         cst = {j - n_num: 1 - 2 * (j % 2) for j in range(a.monotone)}
         run(f"hgbt_mono{a.monotone}[{a.device}]",
-            lambda: HistGBTClassifier(**common, device=a.device, monotone_cst=cst),
+            lambda: HistGBTClassifier(**common, device=a.device, monotone_cst=cst,
+                                      bin_device=a.bin_device),
             repeats=a.repeats)
     try:
         from sklearn.ensemble import HistGradientBoostingClassifier

@@ -13,7 +13,9 @@ which run as HIP kernels (csrc/creditcore_kernels.hip, hgbt_*_kernel) on
 ``device="cpu"``. The two are specified to build identical trees from
 identical integer inputs:
 
-- Features are binned once on the host into u8 bins from f32 edges,
+- Features are binned once into u8 bins from f32 edges (``bin_features`` on
+  the host; ``bin_features_gpu`` on the device returns the same, see
+  ``bin_device``),
   ``bin(x) = #{edges < x}``, so "bin <= b goes left" is exactly
   ``x <= edges[b]`` for every f32 x and ``edges[b]`` is the packed threshold.
   Columns with at most ``max_bins`` distinct values get the midpoints
@@ -75,6 +77,19 @@ MAX_BINS = 256
 SHIFT = 20  # fractional bits of the fixed-point gradients (cpu_ref.HGBT_SHIFT)
 LDS_BUDGET_BYTES = 64 * 1024  # per-block histogram slab; 2 blocks per CU
 TARGET_BLOCKS = 1024  # histogram grid size aimed at when rows are few
+# bin_features_gpu: most rows of one binning launch; a larger matrix runs as
+# several launches over row slices (the digit counters accumulate). Sized by
+# the launch-length rule of creditcore/engine.py (PDP_LAUNCH_PAIRS): no launch
+# longer than 1.25 x the forest_shap launch at its cap measured in the same
+# run. forest_shap at 1024 rows 60.25 ms (bound 75.31 ms); at 4,194,304 rows x
+# 51 columns, the largest shape measured, all ten binning launches of a slice
+# together take 7.67 ms on an MI355X (bench/bin_micro.py,
+# profiles/bench_results/bin_micro.txt), so the longest of them is well inside.
+BIN_LAUNCH_ROWS = 1 << 22
+# bin_device="auto" keeps the host below this many rows. 0: the device always;
+# at 16k rows x 51 columns it already bins in 1.8 ms against 11.4 ms on the
+# host (profiles/bench_results/train_micro_bin_*_20000.txt).
+BIN_AUTO_MIN_ROWS = 0
 
 
 def _to_dense_f32(x) -> np.ndarray:
@@ -85,6 +100,30 @@ def _to_dense_f32(x) -> np.ndarray:
     if x.ndim != 2:
         raise ValueError("expected a 2-D feature matrix")
     return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def _summary_edges(values: np.ndarray, exact: bool, hi=None) -> np.ndarray:
+    """f32 bin edges from a column's summary (pure: the host path and the
+    device path of bin_features_gpu both end here).
+
+    ``exact``: ``values`` are the column's distinct values, ascending; the
+    edges are the f64 midpoints rounded to f32. Otherwise ``values`` are the
+    order statistics srt[(k * n) // max_bins], k = 1 .. max_bins - 1, and
+    ``hi`` is the column's maximum."""
+    values = np.asarray(values, dtype=np.float32)
+    if exact:
+        a, b = values[:-1], values[1:]
+        mid = ((a.astype(np.float64) + b.astype(np.float64)) * 0.5).astype(np.float32)
+        # adjacent floats: the rounded midpoint may land on b; a itself splits
+        return np.where(mid >= b, a, mid).astype(np.float32)
+    cand = np.unique(values)
+    return cand[cand < hi].astype(np.float32)
+
+
+def _rank_positions(n: int, max_bins: int) -> np.ndarray:
+    """Ranks of the quantile edges in the sorted column, int64 (k * n passes
+    2^31 from 8.4 M rows)."""
+    return (np.arange(1, max_bins, dtype=np.int64) * n) // max_bins
 
 
 def _column_edges(col: np.ndarray, max_bins: int) -> np.ndarray:
@@ -99,14 +138,8 @@ def _column_edges(col: np.ndarray, max_bins: int) -> np.ndarray:
         srt = np.sort(col)
         distinct = srt[np.concatenate([[True], srt[1:] != srt[:-1]])]
     if len(distinct) <= max_bins:
-        a, b = distinct[:-1], distinct[1:]
-        mid = ((a.astype(np.float64) + b.astype(np.float64)) * 0.5).astype(np.float32)
-        # adjacent floats: the rounded midpoint may land on b; a itself splits
-        return np.where(mid >= b, a, mid).astype(np.float32)
-    n = len(srt)
-    pos = (np.arange(1, max_bins, dtype=np.int64) * n) // max_bins
-    cand = np.unique(srt[pos])
-    return cand[cand < hi].astype(np.float32)
+        return _summary_edges(distinct, True)
+    return _summary_edges(srt[_rank_positions(len(srt), max_bins)], False, hi)
 
 
 def bin_features(x: np.ndarray, max_bins: int = MAX_BINS):
@@ -127,6 +160,121 @@ def bin_features(x: np.ndarray, max_bins: int = MAX_BINS):
         thr.append(edges)
         thr.append(np.asarray([np.inf], dtype=np.float32))
     return bins, bin_off, np.concatenate(thr).astype(np.float32)
+
+
+def _f32_keys(v: np.ndarray) -> np.ndarray:
+    """Order-preserving u32 keys of finite f32 values (csrc bin_key): sign bit
+    flipped for non-negative values, all bits for negative ones; both zeros
+    share one key."""
+    u = (np.asarray(v, dtype=np.float32) + np.float32(0.0)).view(np.uint32)
+    return np.where(u >> 31, ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def _keys_f32(k: np.ndarray) -> np.ndarray:
+    """The f32 values of u32 keys (inverse of ``_f32_keys``)."""
+    k = np.asarray(k, dtype=np.uint32)
+    return np.where(k >> 31, k ^ np.uint32(0x80000000), ~k).astype(np.uint32).view(np.float32)
+
+
+def _state_edges(state: np.ndarray, n: int, max_bins: int, slots: int) -> np.ndarray:
+    """Edges of one column from the i64 state row bin_select leaves:
+    {slot count, mode, keys[slots], first rank[slots]}."""
+    ns, quantile = int(state[0]), bool(state[1])
+    values = _keys_f32(state[2 : 2 + ns].astype(np.uint32))
+    if not quantile:
+        return _summary_edges(values, True)
+    base = state[2 + slots : 2 + slots + ns]
+    at = np.searchsorted(base, _rank_positions(n, max_bins), side="right") - 1
+    return _summary_edges(values[at], False, values[-1])
+
+
+def bin_features_gpu(x: np.ndarray, max_bins: int = MAX_BINS, device="cuda"):
+    """``bin_features`` on the GPU: the same (bins, bin_off, bin_threshold)
+    for every finite f32 matrix, with ``bins`` a torch.uint8[F, N] tensor that
+    stays on ``device`` (both ``_GpuBackend``s take it as it stands).
+
+    ``x`` is uploaded once. Per group of ``ext.BIN_GROUP_COLS`` columns a
+    multi-rank radix select (csrc bin_select) leaves O(max_bins) numbers per
+    column: the distinct values, or the values at the quantile ranks and the
+    maximum. They come to the host in one copy, ``_summary_edges`` turns them
+    into edges exactly as the host path does, and the edges go back in one
+    copy for the assign kernel. No launch covers more than
+    ``BIN_LAUNCH_ROWS`` rows."""
+    import torch
+
+    from ..ops import gpu
+
+    ext = gpu.ext()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("expected a non-empty 2-D feature matrix")
+    if not 2 <= int(max_bins) <= MAX_BINS:
+        raise ValueError(f"max_bins must be in [2, {MAX_BINS}]")
+    n, n_feat = x.shape
+    dev = torch.device(device)
+    slots, step = int(ext.BIN_SLOTS), int(ext.BIN_GROUP_COLS)
+    launch_rows = max(1, int(BIN_LAUNCH_ROWS))
+    x_d = torch.from_numpy(x).to(dev)
+    bins = torch.empty((n_feat, n), dtype=torch.uint8, device=dev)
+    bin_off = np.zeros(n_feat + 1, dtype=np.int32)
+    thr = []
+    for f0 in range(0, n_feat, step):
+        f1 = min(f0 + step, n_feat)
+        keys, state = gpu.bin_select(x_d, f0, f1, int(max_bins), launch_rows)
+        table = np.zeros((f1 - f0, slots), dtype=np.uint32)
+        for c in range(f1 - f0):
+            edges = _state_edges(state[c], n, int(max_bins), slots)
+            table[c, 0] = len(edges)
+            table[c, 1 : 1 + len(edges)] = _f32_keys(edges)
+            bin_off[f0 + c + 1] = bin_off[f0 + c] + len(edges) + 1
+            thr.append(edges)
+            thr.append(np.asarray([np.inf], dtype=np.float32))
+        ext.bin_assign(
+            keys, torch.from_numpy(table.view(np.int32)).to(dev), bins, f0, launch_rows
+        )
+    return bins, bin_off, np.concatenate(thr).astype(np.float32)
+
+
+BIN_DEVICES = ("auto", "cpu", "cuda")
+last_bin_seconds = 0.0  # wall time of the latest fit's binning (bench/train_micro.py)
+
+
+def resolve_bin_device(bin_device: str, device: str, fit_device: str, n_rows: int) -> str:
+    """Where a fit bins its features: ``device`` is the estimator's parameter,
+    ``fit_device`` what it resolved to. "auto" bins where the model trains,
+    except that a GPU fit below BIN_AUTO_MIN_ROWS rows keeps the host."""
+    if bin_device not in BIN_DEVICES:
+        raise ValueError("bin_device must be 'auto', 'cpu' or 'cuda'")
+    if bin_device == "cuda":
+        if device == "cpu":
+            raise ValueError(
+                "bin_device='cuda' needs device='cuda' or 'auto': the numpy "
+                "backend takes numpy bins"
+            )
+        if fit_device != "cuda":
+            raise RuntimeError("bin_device='cuda' requested but no GPU is visible")
+        return "cuda"
+    if bin_device == "auto" and fit_device == "cuda" and n_rows >= BIN_AUTO_MIN_ROWS:
+        return "cuda"
+    return "cpu"
+
+
+def bin_for_fit(x: np.ndarray, max_bins: int, where: str):
+    """The fit's binning on ``where`` ("cpu" or "cuda", the current GPU)."""
+    global last_bin_seconds
+    import time
+
+    t0 = time.perf_counter()
+    if where == "cuda":
+        import torch
+
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = bin_features_gpu(x, max_bins, dev)
+        torch.cuda.synchronize(dev)
+    else:
+        out = bin_features(x, max_bins)
+    last_bin_seconds = time.perf_counter() - t0
+    return out
 
 
 class _CpuBackend:
@@ -184,14 +332,15 @@ def plan_feature_groups(
 class _GpuBackend:
     """The three level primitives as HIP kernels over torch tensors."""
 
-    def __init__(self, bins: np.ndarray, bin_off: np.ndarray, ext, device):
+    def __init__(self, bins, bin_off: np.ndarray, ext, device):
         import torch
 
         self._torch, self._ext, self.device = torch, ext, device
         self.n_rows = bins.shape[1]
         self.n_bins = np.diff(bin_off)
         self.total_bins = int(bin_off[-1])
-        self.bins = torch.from_numpy(bins).to(device)
+        # u8[F, N]: numpy from bin_features, or the device tensor of bin_features_gpu
+        self.bins = (bins if torch.is_tensor(bins) else torch.from_numpy(bins)).to(device)
         self.bin_off = torch.from_numpy(bin_off).to(device)
         self.rows_per_block = int(ext.HGBT_MAX_ROWS_PER_BLOCK)
         self.lds_bytes = LDS_BUDGET_BYTES
@@ -389,7 +538,10 @@ class HistGBTClassifier(ClassifierMixin, BaseEstimator):
 
     ``device``: "cuda" trains with the HIP kernels, "cpu" with the numpy
     references, "auto" takes the GPU when one is visible; with a visible GPU
-    and no extension it raises ``ExtensionMissing`` and never falls back."""
+    and no extension it raises ``ExtensionMissing`` and never falls back.
+    ``bin_device``: "cuda" bins the features with ``bin_features_gpu``, "cpu"
+    with ``bin_features``, "auto" bins where the model trains; the fitted
+    model is the same either way. "cuda" needs a GPU fit."""
 
     def __init__(
         self,
@@ -402,6 +554,7 @@ class HistGBTClassifier(ClassifierMixin, BaseEstimator):
         random_state=None,
         device="auto",
         monotone_cst=None,
+        bin_device="auto",
     ):
         self.n_estimators = n_estimators
         self.max_depth = max_depth
@@ -412,6 +565,7 @@ class HistGBTClassifier(ClassifierMixin, BaseEstimator):
         self.random_state = random_state
         self.device = device
         self.monotone_cst = monotone_cst
+        self.bin_device = bin_device
 
     # -- training ----------------------------------------------------------
     def _check_params(self):
@@ -427,6 +581,13 @@ class HistGBTClassifier(ClassifierMixin, BaseEstimator):
             raise ValueError("l2 must be >= 0")
         if self.device not in ("auto", "cpu", "cuda"):
             raise ValueError("device must be 'auto', 'cpu' or 'cuda'")
+        if self.bin_device not in BIN_DEVICES:
+            raise ValueError("bin_device must be 'auto', 'cpu' or 'cuda'")
+        if self.bin_device == "cuda" and self.device == "cpu":
+            raise ValueError(
+                "bin_device='cuda' needs device='cuda' or 'auto': the numpy "
+                "backend takes numpy bins"
+            )
 
     def _resolve_monotone(self, n_feat: int) -> np.ndarray:
         """``monotone_cst`` as an i32 sign per encoded column: a sequence of
@@ -487,11 +648,12 @@ class HistGBTClassifier(ClassifierMixin, BaseEstimator):
         self.n_features_in_ = x.shape[1]
         self.monotone_cst_ = self._resolve_monotone(x.shape[1])
 
-        bins, bin_off, bin_thr = bin_features(x, int(self.max_bins))
-        self.bin_offsets_ = bin_off
-        self.bin_thresholds_ = bin_thr
         device = self._resolve_device()
         self.fit_device_ = device
+        where = resolve_bin_device(self.bin_device, self.device, device, len(x))
+        bins, bin_off, bin_thr = bin_for_fit(x, int(self.max_bins), where)
+        self.bin_offsets_ = bin_off
+        self.bin_thresholds_ = bin_thr
         if device == "cuda":
             trees = self._boost_gpu(bins, bin_off, bin_thr, y01)
         else:

@@ -14,8 +14,9 @@ which run as HIP kernels (csrc/creditcore_kernels.hip, hrf_*_kernel) on
 ``device="cpu"``. Nothing between the trees is floating point, so the two
 devices are specified to build byte-identical forests:
 
-- Binning is ``hgbt.bin_features``: "bin <= b goes left" is ``x <= edge`` and
-  the f32 edge is the packed threshold.
+- Binning is ``hgbt.bin_features``, or ``hgbt.bin_features_gpu`` which
+  returns the same on the device (``bin_device``): "bin <= b goes left" is
+  ``x <= edge`` and the f32 edge is the packed threshold.
 - Bagging: tree t weighs row i by its bootstrap count,
   ``bincount(default_rng([random_state, t]).integers(0, N, N))``, drawn on
   the host (u8; ``random_state=None`` counts as 0). ``bootstrap=False``: all
@@ -67,14 +68,16 @@ import numpy as np
 from sklearn.base import BaseEstimator, ClassifierMixin
 
 from .hgbt import (
+    BIN_DEVICES,
     LDS_BUDGET_BYTES,
     MAX_BINS,
     MAX_DEPTH,
     TARGET_BLOCKS,
     _TREE_KEYS,
     _to_dense_f32,
-    bin_features,
+    bin_for_fit,
     plan_feature_groups,
+    resolve_bin_device,
 )
 
 MAX_DEPTH_DEEP = 24  # with deep_trees=True; levels past _dense_levels run segmented
@@ -169,7 +172,7 @@ class _CpuBackend:
 class _GpuBackend:
     """The three level primitives as HIP kernels over torch tensors."""
 
-    def __init__(self, bins: np.ndarray, bin_off: np.ndarray, y: np.ndarray, ext, device):
+    def __init__(self, bins, bin_off: np.ndarray, y: np.ndarray, ext, device):
         import torch
 
         self._torch, self._ext, self.device = torch, ext, device
@@ -184,7 +187,9 @@ class _GpuBackend:
         self._groups: dict = {}
         self._bins_rm = None
 
-    def _dev(self, a: np.ndarray):
+    def _dev(self, a):
+        if self._torch.is_tensor(a):  # the u8 bins of bin_features_gpu
+            return a.to(self.device).contiguous()
         return self._torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
 
     def start(self, w: np.ndarray, node: np.ndarray):
@@ -361,7 +366,9 @@ class HistForestClassifier(ClassifierMixin, BaseEstimator):
 
     ``device``: "cuda" trains with the HIP kernels, "cpu" with the numpy
     references, "auto" takes the GPU when one is visible; with a visible GPU
-    and no extension it raises ``ExtensionMissing`` and never falls back."""
+    and no extension it raises ``ExtensionMissing`` and never falls back.
+    ``bin_device``: where the features are binned ("auto": where the model
+    trains; ``hgbt.resolve_bin_device``); the forest is the same either way."""
 
     _tree_batch = None  # trees per batch; None: from HIST_BUDGET_BYTES
     # a fit deeper than MAX_DEPTH runs its levels from this depth on segmented;
@@ -379,6 +386,7 @@ class HistForestClassifier(ClassifierMixin, BaseEstimator):
         random_state=None,
         device="auto",
         deep_trees=False,
+        bin_device="auto",
     ):
         self.n_estimators = n_estimators
         self.max_depth = max_depth
@@ -389,6 +397,7 @@ class HistForestClassifier(ClassifierMixin, BaseEstimator):
         self.random_state = random_state
         self.device = device
         self.deep_trees = deep_trees
+        self.bin_device = bin_device
 
     # -- training ----------------------------------------------------------
     def _check_params(self):
@@ -405,6 +414,13 @@ class HistForestClassifier(ClassifierMixin, BaseEstimator):
             raise ValueError("random_state must be None or in [0, 2^63)")
         if self.device not in ("auto", "cpu", "cuda"):
             raise ValueError("device must be 'auto', 'cpu' or 'cuda'")
+        if self.bin_device not in BIN_DEVICES:
+            raise ValueError("bin_device must be 'auto', 'cpu' or 'cuda'")
+        if self.bin_device == "cuda" and self.device == "cpu":
+            raise ValueError(
+                "bin_device='cuda' needs device='cuda' or 'auto': the numpy "
+                "backend takes numpy bins"
+            )
 
     def _resolve_device(self) -> str:
         if self.device == "cpu":
@@ -443,11 +459,12 @@ class HistForestClassifier(ClassifierMixin, BaseEstimator):
         y01 = (y == self.classes_[1]).astype(np.uint8)
         self.n_features_in_ = n_feat
 
-        bins, bin_off, bin_thr = bin_features(x, int(self.max_bins))
-        self.bin_offsets_ = bin_off
-        self.bin_thresholds_ = bin_thr
         device = self._resolve_device()
         self.fit_device_ = device
+        where = resolve_bin_device(self.bin_device, self.device, device, n_rows)
+        bins, bin_off, bin_thr = bin_for_fit(x, int(self.max_bins), where)
+        self.bin_offsets_ = bin_off
+        self.bin_thresholds_ = bin_thr
         if device == "cuda":
             import torch
 

@@ -97,3 +97,14 @@ def mmd_perm_w(z, norms, gamma: float, ind, cols_per_block: int, launch_rows: in
         for a in range(0, n, step)
     ]
     return np.concatenate([p.cpu().numpy() for p in parts])  # D2H copies synchronize
+
+
+def bin_select(x, f0: int, f1: int, max_bins: int, launch_rows: int):
+    """bin_select of the extension on the device matrix ``x`` f32[N, F]: the
+    radix-select summary of the columns [f0, f1). Returns ``(keys, state)``:
+    the group's u32 keys i32[G, N], which stay on the device for
+    ``ext().bin_assign``, and the per-column state as numpy i64[G, 2 + 2 *
+    BIN_SLOTS] = {slot count, mode, keys, first ranks} (models/hgbt.py
+    ``_state_edges`` reads it); the summary's only device-to-host copy."""
+    keys, state = ext().bin_select(x, int(f0), int(f1), int(max_bins), int(launch_rows))
+    return keys, state.cpu().numpy()  # the D2H copy synchronizes

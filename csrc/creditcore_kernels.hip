@@ -3315,6 +3315,376 @@ void hgbt_route(torch::Tensor bins, torch::Tensor table, torch::Tensor node)
 }
 
 // ---------------------------------------------------------------------------
+// Feature binning on the device (hgbt.bin_features_gpu): what both trainers
+// consume, u8 bins[F, N], made from the uploaded f32 matrix x[N, F].
+//
+// bin_select summarises a group of at most BIN_GROUP_COLS columns with a
+// multi-rank radix select over order-preserving u32 keys (-0.0 and +0.0 share
+// one key), four 8-bit digit passes from the top:
+//
+//   bin_keys_kernel   x row-major -> keys[G, N] column-major through a
+//                     64 x 64 LDS tile, both sides coalesced (the one extra
+//                     copy of the block);
+//   bin_count_kernel  hist[column][slot][digit] += 1 for every row whose key
+//                     prefix is one of the column's active prefixes (slots);
+//   bin_plan_kernel   one block per column turns the counts into the next
+//                     pass's slot table.
+//
+// A column's state is BIN_ST_WORDS i64 words: {slots, mode, prefix[256],
+// base[256]}; base is the rank of the slot's first key in the sorted column.
+// While a column's non-empty buckets number <= max_bins (mode 0) all of them
+// stay active, and after the last pass they are its distinct values. Once
+// they exceed max_bins the column is a quantile column for good (mode 1):
+// only buckets that hold one of the ranks (k * N) / max_bins, k = 1 ..
+// max_bins - 1, or the last rank N - 1 (the maximum) stay, at most max_bins
+// of them. Counters are integers and accumulate across launches over row
+// slices, so the result does not depend on the order atomics land in.
+//
+// bin_assign_kernel stages a column's edge keys in LDS and writes
+// bins[f][r] = #{edges < x} by binary search over them, from the
+// column-major keys: reads and byte writes are both coalesced.
+//
+// No kernel here computes in floating point: x is read as its bit pattern.
+// ---------------------------------------------------------------------------
+
+#define BIN_BLOCK 256
+#define BIN_SLOTS 256          // most active prefixes of a column (HGBT_MAX_BINS)
+#define BIN_DIGITS 256         // 8-bit digits, four passes
+#define BIN_LDS_SLOTS 60       // counters live in LDS up to this many slots (60 KiB)
+#define BIN_ROWS_PER_BLOCK 16384
+#define BIN_GROUP_COLS 64      // columns of one bin_select call (16 MiB of counters)
+#define BIN_TILE 64
+#define BIN_AGG_ROUNDS 4       // same-address rounds of a wave before plain atomics
+#define BIN_ST_WORDS (2 + 2 * BIN_SLOTS)
+static_assert(BIN_SLOTS == HGBT_MAX_BINS && BIN_SLOTS <= BIN_BLOCK,
+              "one thread per slot stages a column's table");
+static_assert(BIN_DIGITS == BIN_BLOCK, "bin_plan_kernel: one thread per digit");
+static_assert((BIN_LDS_SLOTS * BIN_DIGITS + BIN_SLOTS) * 4 <= 64 * 1024,
+              "static LDS of bin_count_kernel; two blocks per CU");
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BIN_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define BIN_NO_PACKED_F32
+#endif
+
+// Order-preserving key of a finite f32 bit pattern; both zeros give 0x80000000.
+__device__ __forceinline__ unsigned bin_key(unsigned u) {
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// grid = (64-row tiles of the slice [r0, r1), 64-column tiles of the group).
+BIN_NO_PACKED_F32
+__global__ __launch_bounds__(BIN_BLOCK) void bin_keys_kernel(
+    const unsigned* __restrict__ x, long long n_rows, int n_feat, int f0, int g_cols,
+    long long r0, long long r1, unsigned* __restrict__ keys)
+{
+  __shared__ unsigned tile[BIN_TILE][BIN_TILE + 1];
+  const int tx = threadIdx.x & (BIN_TILE - 1), ty = threadIdx.x / BIN_TILE;
+  const long long rb = r0 + (long long)blockIdx.x * BIN_TILE;
+  const int cb = (int)blockIdx.y * BIN_TILE;
+  for (int i = ty; i < BIN_TILE; i += BIN_BLOCK / BIN_TILE) {
+    const long long r = rb + i;
+    const int c = cb + tx;
+    if (r < r1 && c < g_cols)
+      tile[i][tx] = bin_key(x[(size_t)r * (size_t)n_feat + (size_t)(f0 + c)]);
+  }
+  __syncthreads();
+  for (int i = ty; i < BIN_TILE; i += BIN_BLOCK / BIN_TILE) {
+    const int c = cb + i;
+    const long long r = rb + tx;
+    if (c < g_cols && r < r1) keys[(size_t)c * (size_t)n_rows + (size_t)r] = tile[tx][i];
+  }
+}
+
+// One counter increment per lane (idx < 0: none) with same-address
+// aggregation: for up to BIN_AGG_ROUNDS rounds the first pending lane's
+// address is broadcast and every lane holding it retires through one atomic
+// of the group's size; what is left goes on its own. A column of mostly one
+// value costs one atomic per wave instead of 64 on one address. Every lane of
+// the wave must call this.
+__device__ __forceinline__ void bin_wave_add(unsigned* __restrict__ cnt, int idx) {
+  const int lane = threadIdx.x & 63;
+  bool pending = idx >= 0;
+  for (int round = 0; round < BIN_AGG_ROUNDS; ++round) {
+    const unsigned long long act = __ballot(pending);
+    if (!act) return;
+    const int leader = __ffsll((long long)act) - 1;
+    const int lidx = __shfl(idx, leader);
+    const bool same = pending && idx == lidx;
+    const unsigned long long grp = __ballot(same);
+    if (same) {
+      if (lane == leader) atomicAdd(cnt + lidx, (unsigned)__popcll(grp));
+      pending = false;
+    }
+  }
+  if (pending) atomicAdd(cnt + idx, 1u);
+}
+
+// grid = (row blocks of the slice [r0, r1), columns of the group). Digit pass
+// with the digit at bit `shift` (24, 16, 8, 0); the prefix is the key above
+// it. hist is u32[g_cols, BIN_SLOTS, BIN_DIGITS]. Up to BIN_LDS_SLOTS slots
+// the block counts in LDS and flushes its non-zero counters; above, it counts
+// straight into hist. Slot indices come from a bounded search over the
+// clamped table, so no table content can index outside hist.
+BIN_NO_PACKED_F32
+__global__ __launch_bounds__(BIN_BLOCK) void bin_count_kernel(
+    const unsigned* __restrict__ keys, long long n_rows, long long r0, long long r1,
+    int g_cols, int shift, const long long* __restrict__ st,
+    unsigned* __restrict__ hist)
+{
+  __shared__ unsigned s_prefix[BIN_SLOTS];
+  __shared__ unsigned s_cnt[BIN_LDS_SLOTS * BIN_DIGITS];
+  const int c = blockIdx.y, tid = threadIdx.x;
+  if (c >= g_cols) return;
+  const long long* cst = st + (size_t)c * BIN_ST_WORDS;
+  const int ns = (int)min(max(cst[0], 0ll), (long long)BIN_SLOTS);
+  if (ns == 0) return;
+  const bool use_lds = ns <= BIN_LDS_SLOTS;
+  if (tid < ns) s_prefix[tid] = (unsigned)cst[2 + tid];
+  if (use_lds)
+    for (int i = tid; i < ns * BIN_DIGITS; i += BIN_BLOCK) s_cnt[i] = 0u;
+  __syncthreads();
+
+  const unsigned* col = keys + (size_t)c * (size_t)n_rows;
+  unsigned* gh = hist + (size_t)c * BIN_SLOTS * BIN_DIGITS;
+  const long long b0 = r0 + (long long)blockIdx.x * BIN_ROWS_PER_BLOCK;
+  const long long b1 = min(b0 + (long long)BIN_ROWS_PER_BLOCK, r1);
+  // the trip count is the block's: whole waves reach bin_wave_add
+  for (long long rr = b0; rr < b1; rr += BIN_BLOCK) {
+    const long long r = rr + tid;
+    int idx = -1;
+    if (r < b1) {
+      const unsigned k = col[r];
+      const unsigned pre = (shift >= 24) ? 0u : (k >> (shift + 8));
+      int lo = 0, hi = ns;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s_prefix[mid] < pre) lo = mid + 1; else hi = mid;
+      }
+      if (lo < ns && s_prefix[lo] == pre)
+        idx = lo * BIN_DIGITS + (int)((k >> shift) & (BIN_DIGITS - 1));
+    }
+    if (use_lds) {
+      if (idx >= 0) atomicAdd(&s_cnt[idx], 1u);
+    } else {
+      bin_wave_add(gh, idx);
+    }
+  }
+  if (use_lds) {
+    __syncthreads();
+    for (int i = tid; i < ns * BIN_DIGITS; i += BIN_BLOCK) {
+      const unsigned v = s_cnt[i];
+      if (v) atomicAdd(gh + i, v);
+    }
+  }
+}
+
+// Exclusive prefix sum of v over the block's 256 threads and its total.
+__device__ __forceinline__ void bin_block_scan(
+    unsigned v, unsigned* s_wave, unsigned& excl, unsigned& total)
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned inc = v;
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned t = __shfl_up(inc, d);
+    if (lane >= d) inc += t;
+  }
+  __syncthreads();  // the previous scan's readers are done with s_wave
+  if (lane == 63) s_wave[wave] = inc;
+  __syncthreads();
+  unsigned before = 0, tot = 0;
+  for (int w = 0; w < BIN_BLOCK / 64; ++w) {
+    const unsigned t = s_wave[w];
+    if (w < wave) before += t;
+    tot += t;
+  }
+  excl = before + inc - v;
+  total = tot;
+}
+
+// #{k in 1 .. max_bins-1 : (k * n) / max_bins < x} for 0 <= x <= n, in int64.
+__device__ __forceinline__ long long bin_ranks_below(long long x, long long n, int max_bins) {
+  const long long k = (x * max_bins + n - 1) / n - 1;
+  return min(max(k, 0ll), (long long)(max_bins - 1));
+}
+
+// grid = columns of the group; thread = digit. Walks the column's slots in
+// key order; bucket (slot, digit) starts at rank base[slot] + the counts of
+// the slot's lower digits. Kept buckets become the next table, compacted in
+// order; at most BIN_SLOTS are written.
+BIN_NO_PACKED_F32
+__global__ __launch_bounds__(BIN_BLOCK) void bin_plan_kernel(
+    const unsigned* __restrict__ hist, int g_cols, long long n_total, int max_bins,
+    long long* __restrict__ st)
+{
+  __shared__ unsigned s_prefix[BIN_SLOTS];
+  __shared__ long long s_base[BIN_SLOTS];
+  __shared__ unsigned s_wave[BIN_BLOCK / 64];
+  __shared__ int s_nonempty;
+  const int c = blockIdx.x, tid = threadIdx.x;
+  if (c >= g_cols) return;
+  long long* cst = st + (size_t)c * BIN_ST_WORDS;
+  const int ns = (int)min(max(cst[0], 0ll), (long long)BIN_SLOTS);
+  int mode = cst[1] != 0;
+  if (tid < ns) {
+    s_prefix[tid] = (unsigned)cst[2 + tid];
+    s_base[tid] = cst[2 + BIN_SLOTS + tid];
+  }
+  if (tid == 0) s_nonempty = 0;
+  __syncthreads();
+  const unsigned* h = hist + (size_t)c * BIN_SLOTS * BIN_DIGITS;
+  if (mode == 0) {
+    int mine = 0;
+    for (int s = 0; s < ns; ++s) mine += h[s * BIN_DIGITS + tid] != 0u;
+    if (mine) atomicAdd(&s_nonempty, mine);
+    __syncthreads();
+    if (s_nonempty > max_bins) mode = 1;
+  }
+  int out = 0;
+  for (int s = 0; s < ns; ++s) {
+    const unsigned cnt = h[s * BIN_DIGITS + tid];
+    unsigned below, slot_total;
+    bin_block_scan(cnt, s_wave, below, slot_total);
+    const long long b = s_base[s] + (long long)below, e = b + (long long)cnt;
+    bool keep = cnt != 0u;
+    if (keep && mode == 1)
+      keep = e == n_total ||
+             bin_ranks_below(e, n_total, max_bins) > bin_ranks_below(b, n_total, max_bins);
+    unsigned pos, kept;
+    bin_block_scan(keep ? 1u : 0u, s_wave, pos, kept);
+    const int at = out + (int)pos;
+    if (keep && at < BIN_SLOTS) {
+      cst[2 + at] = (long long)((s_prefix[s] << 8) | (unsigned)tid);
+      cst[2 + BIN_SLOTS + at] = b;
+    }
+    out += (int)kept;
+  }
+  if (tid == 0) {
+    cst[0] = min(out, BIN_SLOTS);
+    cst[1] = mode;
+  }
+}
+
+// grid = (row blocks of the slice [r0, r1), columns of the group). edges is
+// i32[g_cols, BIN_SLOTS]: the column's edge count, then its ascending edge
+// keys. bins points at the group's first row of the u8[F, N] matrix.
+BIN_NO_PACKED_F32
+__global__ __launch_bounds__(BIN_BLOCK) void bin_assign_kernel(
+    const unsigned* __restrict__ keys, long long n_rows, long long r0, long long r1,
+    int g_cols, const int* __restrict__ edges, uint8_t* __restrict__ bins)
+{
+  __shared__ unsigned s_edge[BIN_SLOTS];
+  const int c = blockIdx.y, tid = threadIdx.x;
+  if (c >= g_cols) return;
+  const int ne = min(max(edges[(size_t)c * BIN_SLOTS], 0), BIN_SLOTS - 1);
+  if (tid < ne) s_edge[tid] = (unsigned)edges[(size_t)c * BIN_SLOTS + 1 + tid];
+  __syncthreads();
+  const unsigned* col = keys + (size_t)c * (size_t)n_rows;
+  uint8_t* out = bins + (size_t)c * (size_t)n_rows;
+  const long long b0 = r0 + (long long)blockIdx.x * BIN_ROWS_PER_BLOCK;
+  const long long b1 = min(b0 + (long long)BIN_ROWS_PER_BLOCK, r1);
+  for (long long r = b0 + tid; r < b1; r += BIN_BLOCK) {
+    const unsigned k = col[r];
+    int lo = 0, hi = ne;  // #{edges < key}
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (s_edge[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    out[r] = (uint8_t)lo;
+  }
+}
+
+// Summary of the columns [f0, f1) of x f32[N, F]: {keys i32[G, N] (the u32
+// keys, column-major), st i64[G, BIN_ST_WORDS]}. After the four passes a
+// column's slots are whole keys: its distinct values in mode 0; in mode 1 the
+// values that hold the quantile ranks and the maximum, each with the rank of
+// its first occurrence. No launch covers more than launch_rows rows.
+std::vector<torch::Tensor> bin_select(
+    torch::Tensor x, int64_t f0, int64_t f1, int64_t max_bins, int64_t launch_rows)
+{
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kFloat32 && x.dim() == 2 &&
+              x.is_contiguous(), "x must be a contiguous f32[N, F] GPU tensor");
+  const int64_t N = x.size(0), F = x.size(1);
+  TORCH_CHECK(N >= 1 && N < (int64_t(1) << 31), "row count out of range (u32 counters)");
+  TORCH_CHECK(F >= 1 && F < (int64_t(1) << 31), "feature count out of range");
+  TORCH_CHECK(0 <= f0 && f0 < f1 && f1 <= F && f1 - f0 <= BIN_GROUP_COLS,
+              "a column group is [f0, f1) with at most ", BIN_GROUP_COLS, " columns");
+  TORCH_CHECK(max_bins >= 2 && max_bins <= HGBT_MAX_BINS, "max_bins must be in [2, 256]");
+  TORCH_CHECK(launch_rows >= 1, "launch_rows must be >= 1");
+  const int64_t G = f1 - f0;
+  c10::hip::HIPGuard guard((c10::DeviceIndex)x.get_device());
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(x.device());
+  auto keys = torch::empty({G, N}, i32);
+  auto hist = torch::empty({G, BIN_SLOTS, BIN_DIGITS}, i32);
+  auto st = torch::zeros({G, BIN_ST_WORDS}, i32.dtype(torch::kInt64));
+  st.select(1, 0).fill_(1);  // one slot: the empty prefix, base rank 0, mode 0
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  unsigned* kp = reinterpret_cast<unsigned*>(keys.data_ptr<int>());
+  unsigned* hp = reinterpret_cast<unsigned*>(hist.data_ptr<int>());
+  long long* sp = reinterpret_cast<long long*>(st.data_ptr<int64_t>());
+  const int col_tiles = (int)((G + BIN_TILE - 1) / BIN_TILE);
+  for (int64_t a = 0; a < N; a += launch_rows) {
+    const int64_t b = std::min(N, a + launch_rows);
+    hipLaunchKernelGGL(bin_keys_kernel,
+        dim3((unsigned)((b - a + BIN_TILE - 1) / BIN_TILE), (unsigned)col_tiles),
+        dim3(BIN_BLOCK), 0, stream,
+        reinterpret_cast<const unsigned*>(x.data_ptr<float>()), (long long)N, (int)F,
+        (int)f0, (int)G, (long long)a, (long long)b, kp);
+    HIP_CHECK(hipGetLastError());
+  }
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    hist.zero_();
+    for (int64_t a = 0; a < N; a += launch_rows) {
+      const int64_t b = std::min(N, a + launch_rows);
+      hipLaunchKernelGGL(bin_count_kernel,
+          dim3((unsigned)((b - a + BIN_ROWS_PER_BLOCK - 1) / BIN_ROWS_PER_BLOCK), (unsigned)G),
+          dim3(BIN_BLOCK), 0, stream,
+          kp, (long long)N, (long long)a, (long long)b, (int)G, shift, sp, hp);
+      HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(bin_plan_kernel, dim3((unsigned)G), dim3(BIN_BLOCK), 0, stream,
+        hp, (int)G, (long long)N, (int)max_bins, sp);
+    HIP_CHECK(hipGetLastError());
+  }
+  return {keys, st};
+}
+
+// bins[f0 + c][r] = #{edges of column c < key} for the group whose keys
+// bin_select returned; edges i32[G, BIN_SLOTS] = {count, edge keys ...}.
+void bin_assign(torch::Tensor keys, torch::Tensor edges, torch::Tensor bins,
+                int64_t f0, int64_t launch_rows)
+{
+  TORCH_CHECK(bins.is_cuda() && bins.scalar_type() == torch::kUInt8 &&
+              bins.dim() == 2 && bins.is_contiguous(),
+              "bins must be a contiguous u8[F, N] GPU tensor");
+  hgbt_check(keys, bins, torch::kInt32, "keys");
+  hgbt_check(edges, bins, torch::kInt32, "edges");
+  const int64_t N = bins.size(1);
+  TORCH_CHECK(keys.dim() == 2 && keys.size(1) == N && keys.size(0) >= 1,
+              "keys must be i32[G, N]");
+  const int64_t G = keys.size(0);
+  TORCH_CHECK(edges.dim() == 2 && edges.size(0) == G && edges.size(1) == BIN_SLOTS,
+              "edges must be i32[G, ", BIN_SLOTS, "]");
+  TORCH_CHECK(f0 >= 0 && f0 + G <= bins.size(0), "column group outside the bin matrix");
+  TORCH_CHECK(launch_rows >= 1, "launch_rows must be >= 1");
+  if (N == 0) return;
+  c10::hip::HIPGuard guard((c10::DeviceIndex)bins.get_device());
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  for (int64_t a = 0; a < N; a += launch_rows) {
+    const int64_t b = std::min(N, a + launch_rows);
+    hipLaunchKernelGGL(bin_assign_kernel,
+        dim3((unsigned)((b - a + BIN_ROWS_PER_BLOCK - 1) / BIN_ROWS_PER_BLOCK), (unsigned)G),
+        dim3(BIN_BLOCK), 0, stream,
+        reinterpret_cast<const unsigned*>(keys.data_ptr<int>()), (long long)N,
+        (long long)a, (long long)b, (int)G, edges.data_ptr<int>(),
+        bins.data_ptr<uint8_t>() + (size_t)f0 * (size_t)N);
+    HIP_CHECK(hipGetLastError());
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Histogram random-forest trainer (creditcore/models/hrf.py).
 //
 // A forest's trees are independent, so a batch of TB trees grows in the same
@@ -6022,6 +6392,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("HGBT_SHIFT") = py::int_(HGBT_SHIFT);
   m.attr("HGBT_MAX_ROWS_PER_BLOCK") = py::int_(HGBT_MAX_ROWS_PER_BLOCK);
   m.attr("HGBT_LDS_BYTES_MAX") = py::int_(HGBT_LDS_BYTES_MAX);
+  m.def("bin_select", &bin_select,
+        "Binning summary of the columns [f0, f1) of x f32[N,F] by multi-rank "
+        "radix select -> {keys i32[G,N], state i64[G,BIN_ST_WORDS]} (gfx950)",
+        py::arg("x"), py::arg("f0"), py::arg("f1"), py::arg("max_bins"),
+        py::arg("launch_rows"));
+  m.def("bin_assign", &bin_assign,
+        "u8 bins of a column group from its keys and edge keys, written into "
+        "bins[f0:f0+G] (gfx950)",
+        py::arg("keys"), py::arg("edges"), py::arg("bins"), py::arg("f0"),
+        py::arg("launch_rows"));
+  m.attr("BIN_GROUP_COLS") = py::int_(BIN_GROUP_COLS);
+  m.attr("BIN_SLOTS") = py::int_(BIN_SLOTS);
   m.def("hrf_hist", &hrf_hist,
         "HistForest level histogram i64[n_slots,2,total_bins] of a tree batch "
         "(gfx950)",
