@@ -21,6 +21,7 @@ setup(
         CUDAExtension(
             name="creditcore._ccore",
             sources=["csrc/creditcore_kernels.hip"],
+            depends=["csrc/host_codec.h"],
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],
                 # CREDITCORE_ASAN=1: host-side AddressSanitizer debug build

@@ -161,6 +161,65 @@ def test_score_json_full_matches_staged(packed):
 
 
 @pytest.mark.gpu
+def test_score_json_full_on_corpus_bodies(packed):
+    """The one-call path on bodies of tests/_json_cases.py: accepted ones
+    answer as score_encoded_bytes does on the pydantic path's arrays;
+    bodies that go wrong after the array has opened raise ValueError and
+    leave the engine answering the next request correctly."""
+    import json
+
+    from pydantic import TypeAdapter
+
+    from _json_cases import corpus
+    from creditcore.engine import ScoringEngine
+    from creditcore.ops import cpu_ref
+
+    adapter = TypeAdapter(list[LoanApplicant])
+
+    def oracle(body):
+        recs = [r.__dict__ for r in adapter.validate_json(body)]
+        c, n = encode_batch(recs, packed.vocabs)
+        return np.ascontiguousarray(c, np.int16), np.ascontiguousarray(n, np.float32)
+
+    cases = dict(corpus())
+    good = [cases["base/one"], cases["base/shuffled"], cases["base/three"]]
+    for name, body in cases.items():  # the first two small random bodies
+        if len(good) < 5 and name.startswith("rand/"):
+            _, n = oracle(body)
+            if len(n) <= 3 and np.isfinite(n).all():
+                good.append(body)
+    assert len(good) == 5
+
+    eng = ScoringEngine(packed, device="cuda")
+    for body in good:
+        codes, nums = oracle(body)
+        assert 1 <= len(codes) <= 3
+        full = eng.score_json_full(body)
+        staged = eng.score_encoded_bytes(codes, nums)
+        assert full["rows"] == staged["rows"] == len(codes)
+        assert json.loads(full["response_bytes"]) == json.loads(staged["response_bytes"])
+
+    three = cases["base/three"]
+    cut = three.index(b"}, {") + 40  # inside the second record
+    bad = [
+        three[:cut],
+        b'[{"sex": "male"}, {"age": nan}]',
+        b'[{"sex": "ma\\xle"}]',
+        b'[{"x": [}], "age": 1}]',
+        b'[{"sex": "male"}, {"education": "a\x01b"}]',
+    ]
+    for body in bad:
+        with pytest.raises(ValueError):
+            eng.score_json_full(body)
+
+    codes, nums = oracle(three)
+    resp = json.loads(eng.score_json_full(three)["response_bytes"])
+    ref = cpu_ref.score_batch_cpu(packed, codes, nums)
+    np.testing.assert_allclose(resp["predictions"], ref["predictions"], atol=1e-9)
+    np.testing.assert_array_equal(resp["outliers"], ref["outliers"])
+
+
+@pytest.mark.gpu
 def test_slot_pipeline_matches_sync(packed):
     """submit_encoded_slot/finish_slot (double-buffered async path) must
     produce byte-identical responses to the synchronous path, including
