@@ -227,6 +227,16 @@ class ScoringEngine:
     # launch 4.36 ms on an MI355X. The caps allow no larger call, so today no
     # call is sliced.
     MMD_LAUNCH_ROWS = 32768
+    # knn_outliers: most batch rows (64-row tiles) of one knn_topk launch; a
+    # call above it runs as several launches over row slices. Same rule: the
+    # launch at the caps (B = M = 16384, flagship D, k = 32) may take no
+    # longer than 1.25 x the method="shap" launch at SHAP_MAX_ROWS measured
+    # in the same run (bench/knn_micro.py,
+    # profiles/bench_results/knn_micro.txt): forest_shap at 1024 rows
+    # 59.78 ms (bound 74.73 ms), knn_topk at B = M = 16384, k = 32 as one
+    # launch 2.70 ms on an MI355X. The caps allow no larger call, so today no
+    # call is sliced.
+    KNN_LAUNCH_ROWS = 16384
 
     def __init__(
         self,
@@ -257,6 +267,9 @@ class ScoringEngine:
         self._cf_dev = None
         # mmd_drift: (key, mu, sd, z_ref, gamma) of the last reference sample
         self._mmd_ref = None
+        # knn_outliers: the last (reference, k) seen: its embedding, device
+        # copy and leave-one-out neighbour distances
+        self._knn_ref = None
         if device == "cuda":
             self._init_gpu()
 
@@ -1429,6 +1442,130 @@ class ScoringEngine:
         if reference is not None:
             reference = encode_batch(reference, self.packed.vocabs)
         return self.mmd_drift(codes, nums, reference=reference, **kw)
+
+    # ------------------------------------------------- nearest-neighbour outliers
+    def knn_outliers(
+        self,
+        codes: np.ndarray,
+        nums: np.ndarray,
+        reference=None,
+        k: int = 10,
+        score: str = "kth",
+        fpr: float = 0.05,
+        neighbors: bool = False,
+        cols_per_block: int | None = None,
+    ) -> dict:
+        """Nearest-neighbour outlier scores of a batch against a reference
+        sample (alibi-detect's ``KNN``; creditcore/knn.py holds the
+        definition): ``instance_score`` is the distance to the k-th nearest
+        reference row in the MMD embedding (``score="mean"``: the mean of the
+        k distances), ``threshold`` the ``1 - fpr`` quantile of the
+        reference's own leave-one-out scores, ``is_outlier`` their comparison.
+        Independent of the classifier and of the isolation forest behind
+        /predict's ``outliers`` field.
+
+        ``reference`` defaults to the pack's background sample
+        (ExplainUnavailable without one); ``(codes, nums)`` overrides it. The
+        neighbour search runs in knn_topk_kernel on a GPU engine and in
+        cpu_ref.knn_topk_cpu on a CPU engine; everything else is shared host
+        code. Returns ``instance_score`` f64[B], ``is_outlier`` i8[B],
+        ``threshold``, ``k``, ``score``, ``fpr``, ``n``, ``n_ref`` and, with
+        ``neighbors=True``, ``neighbor_index`` i32[B, k] (row numbers of the
+        reference sample, nearest first, ties to the lower row) and
+        ``neighbor_distance`` f64[B, k]. The scoring session is not touched.
+        Caps (creditcore/knn.py) raise ExplainTooLarge; bad arguments and
+        rows that do not embed to finite f32 values raise ValueError."""
+        from . import knn, mmd
+
+        p = self.packed
+        codes, nums = mmd.check_rows(codes, nums, "batch", 1, "knn_outliers")
+        if len(codes) > knn.KNN_MAX_ROWS:
+            raise ExplainTooLarge(
+                f"knn_outliers is capped at {knn.KNN_MAX_ROWS} batch rows (got {len(codes)})"
+            )
+        if reference is None:
+            if p.bg_codes is None or p.bg_nums is None:
+                raise ExplainUnavailable(
+                    "model was packed without a background sample; re-train and "
+                    "re-pack, or pass reference=(codes, nums)"
+                )
+            reference = (p.bg_codes, p.bg_nums)
+        ref_codes, ref_nums = mmd.check_rows(
+            reference[0], reference[1], "reference", 2, "knn_outliers"
+        )
+        if len(ref_codes) > knn.KNN_MAX_REFERENCE:
+            raise ExplainTooLarge(
+                f"knn_outliers is capped at {knn.KNN_MAX_REFERENCE} reference rows "
+                f"(got {len(ref_codes)})"
+            )
+        k, score, fpr = knn.check_args(k, score, fpr, len(ref_codes))
+        with self._explain_lock:
+            ref = self._knn_reference(ref_codes, ref_nums, k, cols_per_block)
+            z_batch = mmd.check_embedding(
+                mmd.embed(p, codes, nums, ref["mu"], ref["sd"]), "batch"
+            )
+            d2, idx = self._knn_topk(z_batch, ref, k, False, cols_per_block)
+        return knn.result(d2, idx, ref["loo_d2"], k, score, fpr, bool(neighbors))
+
+    def _knn_reference(self, ref_codes, ref_nums, k: int, cols_per_block=None) -> dict:
+        """Embedding, device copy and leave-one-out neighbour distances of a
+        reference sample, kept for the last (sample, k) seen; the caller
+        holds _explain_lock."""
+        import hashlib
+
+        from . import mmd
+
+        key = (hashlib.sha1(ref_codes.tobytes() + ref_nums.tobytes()).digest(), k)
+        if self._knn_ref is None or self._knn_ref["key"] != key:
+            mu, sd = mmd.reference_scale(self.packed, ref_nums)
+            z_ref = mmd.embed(self.packed, ref_codes, ref_nums, mu, sd)
+            mmd.check_embedding(z_ref, "reference")  # before it can be cached
+            ref = {"key": key, "mu": mu, "sd": sd, "z": z_ref}
+            if self.device == "cuda":
+                ref["dev"] = self._knn_upload(z_ref)
+            ref["loo_d2"], _ = self._knn_topk(z_ref, ref, k, True, cols_per_block)
+            self._knn_ref = ref
+        return self._knn_ref
+
+    def _knn_upload(self, z: np.ndarray):
+        """(z padded to the kernel's float4 columns, squared norms) on this
+        engine's device; the norms are f64 sums rounded once to f32."""
+        import torch
+
+        from . import mmd
+
+        dev = torch.device("cuda", self.device_index)
+        return (
+            torch.from_numpy(mmd.pad_columns(z)).to(dev),
+            torch.from_numpy(mmd.squared_norms(z).astype(np.float32)).to(dev),
+        )
+
+    def _knn_topk(self, z_batch, ref: dict, k: int, exclude_self: bool, cols_per_block=None):
+        """(d2 f64[B, k], idx i32[B, k]) of z_batch against the reference on
+        this engine's device; with exclude_self z_batch is the reference."""
+        if self.device != "cuda":
+            return cpu_ref.knn_topk_cpu(z_batch, ref["z"], k, exclude_self)
+        import torch
+
+        from .ops import gpu
+
+        zr, nr = ref["dev"]
+        zb, nb = (zr, nr) if exclude_self else self._knn_upload(z_batch)
+        with torch.cuda.device(torch.device("cuda", self.device_index)):
+            d2, idx = gpu.knn_topk(
+                zb, zr, nb, nr, k, exclude_self,
+                cols_per_block=int(cols_per_block or 0),
+                launch_rows=int(self.KNN_LAUNCH_ROWS),
+            )
+        return d2.astype(np.float64), idx
+
+    def knn_outliers_records(self, records, reference=None, **kw) -> dict:
+        """knn_outliers on a request body (list of dicts / DataFrame);
+        ``reference`` likewise, encoded with the same vocabulary."""
+        codes, nums = encode_batch(records, self.packed.vocabs)
+        if reference is not None:
+            reference = encode_batch(reference, self.packed.vocabs)
+        return self.knn_outliers(codes, nums, reference=reference, **kw)
 
     def permutation_importance_records(self, records, labels, **kw) -> dict:
         """permutation_importance on a request body (list of dicts /

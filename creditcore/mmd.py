@@ -27,14 +27,15 @@ MMD_TILE = 64  # rows of a kernel tile; cols_per_block is a multiple of it
 _ONE_HOT = np.float32(np.sqrt(0.5))  # a category mismatch adds 1 to d^2
 
 
-def check_rows(codes, nums, what: str):
+def check_rows(codes, nums, what: str, min_rows: int = 2, caller: str = "mmd_drift"):
     codes = np.ascontiguousarray(codes, dtype=np.int16)
     nums = np.ascontiguousarray(nums, dtype=np.float32)
     r = len(codes)
     if codes.shape != (r, N_CAT) or nums.shape != (r, N_NUM):
         raise ValueError(f"{what} must be (codes [R, {N_CAT}], nums [R, {N_NUM}])")
-    if r < 2:
-        raise ValueError(f"mmd_drift needs at least two {what} rows (got {r})")
+    if r < min_rows:
+        least = "two" if min_rows == 2 else str(min_rows)
+        raise ValueError(f"{caller} needs at least {least} {what} rows (got {r})")
     if np.isinf(nums).any():  # NaN is a missing value and is imputed
         raise ValueError(f"{what} rows hold an infinite numeric")
     return codes, nums

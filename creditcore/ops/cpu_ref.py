@@ -1263,3 +1263,43 @@ def mmd_perm_w_cpu(
         k[np.arange(b - a), np.arange(a, b)] = 0.0
         w[a:b] = k @ ind
     return w
+
+
+def knn_topk_cpu(
+    z_batch: np.ndarray,
+    z_ref: np.ndarray,
+    k: int,
+    exclude_self: bool = False,
+    max_bytes: int = 64 << 20,
+):
+    """The k nearest reference rows of every batch row (creditcore/knn.py;
+    knn_topk_kernel on the GPU) as ``(d2 f64[B, k], idx i32[B, k])``, in f64
+    throughout: ``d2[i, j] = max(|z_i|^2 + |z_j|^2 - 2 z_i . z_j, 0)``, the k
+    smallest ``(d2, j)`` per row in ascending order, so equal distances go to
+    the lower j. ``exclude_self`` leaves out the pair j == i by index (both
+    sides must then be the same rows). Chunked over batch rows: it never holds
+    more than ``max_bytes`` of distances."""
+    zb = np.asarray(z_batch, dtype=np.float64)
+    zr = np.asarray(z_ref, dtype=np.float64)
+    if zb.ndim != 2 or zr.ndim != 2 or zb.shape[1] != zr.shape[1]:
+        raise ValueError("z_batch must be [B, D] and z_ref [M, D]")
+    b, m = len(zb), len(zr)
+    if exclude_self and (zb.shape != zr.shape or not np.array_equal(zb, zr)):
+        raise ValueError("exclude_self needs the same rows on both sides")
+    k = int(k)
+    if not 1 <= k <= m - (1 if exclude_self else 0):
+        raise ValueError(f"k must be in [1, {m - (1 if exclude_self else 0)}] (got {k})")
+    nb = np.einsum("ij,ij->i", zb, zb)
+    nr = np.einsum("ij,ij->i", zr, zr)
+    d2 = np.empty((b, k), dtype=np.float64)
+    idx = np.empty((b, k), dtype=np.int32)
+    step = max(1, int(max_bytes) // (8 * m))
+    for a in range(0, b, step):
+        e = min(a + step, b)
+        d = np.maximum(nb[a:e, None] + nr[None, :] - 2.0 * (zb[a:e] @ zr.T), 0.0)
+        if exclude_self:
+            d[np.arange(e - a), np.arange(a, e)] = np.inf
+        order = np.argsort(d, axis=1, kind="stable")[:, :k]
+        idx[a:e] = order
+        d2[a:e] = np.take_along_axis(d, order, axis=1)
+    return d2, idx

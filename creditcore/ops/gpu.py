@@ -99,6 +99,40 @@ def mmd_perm_w(z, norms, gamma: float, ind, cols_per_block: int, launch_rows: in
     return np.concatenate([p.cpu().numpy() for p in parts])  # D2H copies synchronize
 
 
+def knn_topk(
+    z_batch,
+    z_ref,
+    norms_batch,
+    norms_ref,
+    k: int,
+    exclude_self: bool = False,
+    cols_per_block: int = 0,
+    launch_rows: int = 0,
+):
+    """knn_topk of the extension on device tensors (z_batch f32[B, Dp], z_ref
+    f32[M, Dp], their squared norms f32[B] and f32[M]): the k nearest
+    reference rows per batch row as numpy ``(d2 f32[B, k], idx i32[B, k])``,
+    ascending in (d2, j). ``cols_per_block`` (a multiple of the 64-row tile;
+    0 picks knn.default_cols_per_block) is the reference slice of one block
+    and does not change the result; ``launch_rows`` > 0 runs it as several
+    launches over slices of that many batch rows (a multiple of the tile)."""
+    import numpy as np
+
+    from ..knn import default_cols_per_block
+
+    b, m = int(z_batch.shape[0]), int(z_ref.shape[0])
+    cols = int(cols_per_block) or default_cols_per_block(b, m)
+    step = int(launch_rows) if launch_rows and launch_rows < b else b
+    parts = [
+        ext().knn_topk(z_batch, z_ref, norms_batch, norms_ref, int(k),
+                       bool(exclude_self), cols, a, min(step, b - a))
+        for a in range(0, b, step)
+    ]
+    # D2H copies synchronize
+    return (np.concatenate([p[0].cpu().numpy() for p in parts]),
+            np.concatenate([p[1].cpu().numpy() for p in parts]))
+
+
 def bin_select(x, f0: int, f1: int, max_bins: int, launch_rows: int):
     """bin_select of the extension on the device matrix ``x`` f32[N, F]: the
     radix-select summary of the columns [f0, f1). Returns ``(keys, state)``:

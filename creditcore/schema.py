@@ -362,6 +362,39 @@ class MmdDriftOutput(BaseModel):
     n_permutations: int
 
 
+class KnnOutlierRequest(BaseModel):
+    """POST /outlier/knn request: the records as /score takes them, the
+    number of neighbours, the score (``kth`` or ``mean``), the false-positive
+    rate behind the threshold, and whether to return the neighbours."""
+
+    records: list[dict]
+    k: int = 10
+    score: str = "kth"
+    fpr: float = 0.05
+    neighbors: bool = False
+
+    model_config = ConfigDict(extra="ignore")
+
+
+class KnnOutlierOutput(BaseModel):
+    """POST /outlier/knn response: per record the distance to its k-th
+    nearest row of the packed reference sample (or the mean of the k
+    distances) and its comparison with ``threshold``, the ``1 - fpr``
+    quantile of the sample's own leave-one-out scores. ``neighbor_index``
+    holds row numbers of the reference sample, nearest first."""
+
+    instance_score: list[float]
+    is_outlier: list[int]
+    threshold: float
+    k: int
+    score: str
+    fpr: float
+    n: int
+    n_ref: int
+    neighbor_index: list[list[int]] | None = None
+    neighbor_distance: list[list[float]] | None = None
+
+
 # The one-record CI smoke-test fixture (reference app/sample-request.json).
 SAMPLE_REQUEST: list[dict] = [
     {

@@ -45,6 +45,8 @@ from .schema import (
     ExplainOutput,
     ImportanceOutput,
     ImportanceRequest,
+    KnnOutlierOutput,
+    KnnOutlierRequest,
     LoanApplicant,
     MmdDriftOutput,
     MmdDriftRequest,
@@ -958,6 +960,67 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
             raise HTTPException(status_code=500, detail=f"mmd drift failed: {e}")
         metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
         return _json_response(out)
+
+    @app.post("/outlier/knn", response_model=KnnOutlierOutput)
+    async def outlier_knn(req: KnnOutlierRequest):
+        """Nearest-neighbour outlier scores of the posted records against the
+        model's packed background sample (ScoringEngine.knn_outliers).
+        Stateless: it touches neither /predict's ``outliers`` field nor the
+        scoring session. One attempt on one live replica; bypasses the
+        micro-batcher."""
+        import asyncio
+
+        from .knn import KNN_MAX_ROWS
+
+        metrics: Metrics = state["metrics"]
+        engines = state["engines"]
+        pool: ReplicaPool = state["pool"]
+        packed = engines[0].packed
+        if packed.bg_codes is None or packed.bg_nums is None:
+            raise HTTPException(
+                status_code=501,
+                detail="the served model was packed without a background sample; "
+                "re-train and re-pack it to enable /outlier/knn",
+            )
+        if len(req.records) > KNN_MAX_ROWS:
+            raise HTTPException(
+                status_code=413, detail=f"/outlier/knn takes at most {KNN_MAX_ROWS} rows"
+            )
+        if len(req.records) < 1:
+            raise HTTPException(status_code=422, detail="/outlier/knn needs at least one row")
+        try:
+            codes, nums = encode_batch(req.records, packed.vocabs)
+        except (ValueError, TypeError, KeyError) as e:
+            raise HTTPException(status_code=422, detail=f"bad record: {e}")
+        try:
+            idx = pool.pick()
+        except RuntimeError:
+            metrics.observe_error()
+            raise HTTPException(status_code=503, detail="no healthy replicas")
+        t0 = time.perf_counter()
+
+        def call():
+            return engines[idx].knn_outliers(
+                codes, nums, k=req.k, score=req.score, fpr=req.fpr, neighbors=req.neighbors
+            )
+
+        try:
+            out = await asyncio.get_running_loop().run_in_executor(None, call)
+            pool.report_ok(idx)
+        except ExplainTooLarge as e:  # the request's fault, not the replica's
+            raise HTTPException(status_code=413, detail=str(e))
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        except ExplainUnavailable as e:
+            raise HTTPException(status_code=501, detail=str(e))
+        except Exception as e:
+            metrics.observe_error()
+            pool.report_fail(idx)
+            raise HTTPException(status_code=500, detail=f"knn outliers failed: {e}")
+        metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
+        return _json_response(
+            {key: v.tolist() if isinstance(v, np.ndarray) else v for key, v in out.items()}
+        )
 
     @app.get("/healthz")
     async def healthz(deep: bool = False):

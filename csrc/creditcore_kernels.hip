@@ -4986,6 +4986,350 @@ torch::Tensor mmd_perm_w(torch::Tensor z, torch::Tensor norms, double gamma,
 }
 
 // ---------------------------------------------------------------------------
+// Nearest-neighbour outlier scores (creditcore/knn.py): the k smallest
+// squared distances from every batch row to the rows of a reference sample,
+// without ever holding the B x M distance matrix (1 GiB in f32 at the caps).
+//
+//   GEMM      S[j, i] = zr_j . zb_i   (f32 matrix cores, transposed as in
+//                                      mmd_perm_kernel, same LDS d-chunks)
+//   epilogue  d2 = max(n_i + n_j - 2 S, 0); key = bits(d2) << 32 | j
+//   select    per batch row i the k smallest keys of the block's columns
+//
+// A 256-thread block owns 64 batch rows i (16 per wave) and the reference
+// columns j in [y * cols_per_block, ...), walked in tiles of 64. Because the
+// distance tile is computed transposed, accumulator register r of MFMA js is
+// d2[j = j0 + 16 js + 4 g + r][i = h]: all 16 accumulators of a lane belong
+// to ONE batch row, and the four lanes h, h + 16, h + 32, h + 48 hold that
+// row's 64 columns of the tile. A wave therefore selects for its own 16 rows
+// with no help from the other waves, and the selection needs no block
+// barrier.
+//
+// Selection state per row, in LDS: KNN_SLOTS u64 keys, slots [0, 32) the
+// sorted best so far (+inf keys at the start), slots [32, 56) pending
+// candidates. Each lane keeps its row's bound tau (the key in slot k - 1)
+// and the pending count in registers, identical in the row's four lanes. Per
+// 16-row step js a lane tests its four keys against tau; the survivors'
+// positions in the pending area come from the four lanes' counts exchanged
+// by shuffles (lower g first), not from an atomic. A row whose pending area
+// cannot take the step's keys (at most 16) is flushed first: the 64 lanes
+// take one slot each, rank their key among the k best and the pending ones
+// by broadcast reads (ties, which only the +inf keys have, go to the lower
+// slot), and the ranks below k are written back in order; slots [k, 32) stay
+// +inf. tau falls quickly: past the first tiles a whole wave usually has no
+// survivor and skips everything after the compare.
+//
+// The order is that of the u64 key throughout, so equal distances go to the
+// lower j, and the result does not depend on cols_per_block or on timing.
+// Every block writes its rows' sorted k keys to part[y][i][0 .. k);
+// knn_merge_kernel (one wave per row) merges the splits' lists.
+// ---------------------------------------------------------------------------
+
+#define KNN_BLOCK 256
+#define KNN_TILE 64        // batch rows of a block; reference rows of a step
+#define KNN_DC 64          // d-chunk staged in LDS
+#define KNN_ZLD 68         // LDS row stride of a z tile (floats), as MMD_ZLD
+#define KNN_MAX_K 32
+#define KNN_SLOTS 56       // per row: KNN_MAX_K best, then the pending keys
+#define KNN_PENDING (KNN_SLOTS - KNN_MAX_K)  // >= 16, what one step can add
+#define KNN_MAX_ROWS 16384
+#define KNN_MAX_SPLITS (KNN_MAX_ROWS / KNN_TILE)  // 4 list heads per merge lane
+#define KNN_MAX_DP 4096
+#define KNN_INF_KEY 0x7f800000ffffffffull  // d2 = +inf, j = -1
+
+typedef unsigned long long knn_key;
+
+// Orders a wave's LDS traffic: LDS serves one wave's instructions in issue
+// order, so all that is needed is that the compiler keeps that order.
+__device__ __forceinline__ void knn_wave_sync()
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Sorts row `row` of the wave (uniform): slots [0, 32) and `pending` more.
+// Returns the key of slot k - 1 afterwards. Called by all 64 lanes.
+__device__ __forceinline__ knn_key knn_flush_row(knn_key* __restrict__ keys,
+                                                 int pending, int k, int lane)
+{
+  // slots [k, 32) are never written: they hold +inf and are left out
+  const bool live = lane < k || (lane >= KNN_MAX_K && lane < KNN_MAX_K + pending);
+  const knn_key mine = live ? keys[lane] : KNN_INF_KEY;
+  int rank = 0;
+#pragma unroll
+  for (int part = 0; part < 2; ++part) {
+    const int lo = part ? KNN_MAX_K : 0, hi = part ? KNN_MAX_K + pending : k;
+    for (int m0 = lo; m0 < hi; m0 += 8) {  // uniform; eight broadcast reads in flight
+      knn_key other[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) other[u] = keys[min(m0 + u, hi - 1)];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int m = m0 + u;
+        rank += (m < hi && (other[u] < mine || (other[u] == mine && m < lane))) ? 1 : 0;
+      }
+    }
+  }
+  knn_wave_sync();  // every read is done before a slot changes
+  if (live && rank < k) keys[rank] = mine;
+  knn_wave_sync();
+  return keys[k - 1];
+}
+
+MMD_NO_PACKED_F32 __global__ __launch_bounds__(KNN_BLOCK) void knn_topk_kernel(
+    const float* __restrict__ zb,       // [B, Dp] batch rows
+    const float* __restrict__ zr,       // [M, Dp] reference rows
+    const float* __restrict__ norms_b,  // [B]
+    const float* __restrict__ norms_r,  // [Mp], 0 past M
+    knn_key* __restrict__ part,         // [splits, rows, k]
+    int B, int M, int Dp, int k, int cols_per_block, int row0, int rows,
+    int exclude_self)
+{
+  __shared__ __attribute__((aligned(16))) float zi_s[KNN_TILE * KNN_ZLD];
+  __shared__ __attribute__((aligned(16))) float zj_s[KNN_TILE * KNN_ZLD];
+  __shared__ knn_key keys_s[KNN_TILE * KNN_SLOTS];
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int h = lane & 15, g = lane >> 4;
+  const int i_base = row0 + (int)blockIdx.x * KNN_TILE;
+  const int my_i = i_base + wave * 16 + h;
+  const int j_begin = (int)blockIdx.y * cols_per_block;
+  const int j_end = min(j_begin + cols_per_block, M);
+  const bool i_ok = my_i < B && my_i < row0 + rows;
+  const float n_i = norms_b[min(my_i, B - 1)];
+  const int self_j = exclude_self ? my_i : -1;
+  const int ld_c = tid & 15, ld_r = tid >> 4;
+  const bool zi_once = Dp <= KNN_DC;
+  knn_key* const wave_keys = keys_s + wave * 16 * KNN_SLOTS;
+  knn_key* const my_keys = wave_keys + h * KNN_SLOTS;
+
+  // the wave's own 16 x 32 best slots start at +inf
+  for (int e = lane; e < 16 * KNN_MAX_K; e += 64)
+    wave_keys[(e >> 5) * KNN_SLOTS + (e & 31)] = KNN_INF_KEY;
+  knn_wave_sync();
+  knn_key tau = KNN_INF_KEY;  // of row h; the same in its four lanes
+  int pending = 0;            // likewise
+
+  for (int j0 = j_begin; j0 < j_end; j0 += KNN_TILE) {
+    mmd_f4 s[4];
+#pragma unroll
+    for (int js = 0; js < 4; ++js) s[js] = mmd_f4{0.f, 0.f, 0.f, 0.f};
+
+    for (int d0 = 0; d0 < Dp; d0 += KNN_DC) {
+      __syncthreads();  // the previous chunk (and tile) is consumed
+      const int d = d0 + 4 * ld_c;  // Dp % 4 == 0: d < Dp covers d + 3
+      const bool load_i = !zi_once || j0 == j_begin;  // uniform
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int row = ld_r + 16 * q;
+        const int gi = i_base + row, gj = j0 + row;
+        mmd_f4 vi = mmd_f4{0.f, 0.f, 0.f, 0.f}, vj = vi;
+        if (load_i && d < Dp && gi < B)
+          vi = *reinterpret_cast<const mmd_f4*>(zb + (size_t)gi * Dp + d);
+        if (d < Dp && gj < M)
+          vj = *reinterpret_cast<const mmd_f4*>(zr + (size_t)gj * Dp + d);
+        if (load_i)
+          *reinterpret_cast<mmd_f4*>(&zi_s[row * KNN_ZLD + 4 * ld_c]) = vi;
+        *reinterpret_cast<mmd_f4*>(&zj_s[row * KNN_ZLD + 4 * ld_c]) = vj;
+      }
+      __syncthreads();
+
+#pragma unroll
+      for (int kk = 0; kk < KNN_DC / 16; ++kk) {
+        if (d0 + kk * 16 >= Dp) continue;  // uniform
+        const mmd_f4 b = *reinterpret_cast<const mmd_f4*>(
+            &zi_s[(wave * 16 + h) * KNN_ZLD + kk * 16 + 4 * g]);
+#pragma unroll
+        for (int js = 0; js < 4; ++js) {
+          const mmd_f4 a = *reinterpret_cast<const mmd_f4*>(
+              &zj_s[(js * 16 + h) * KNN_ZLD + kk * 16 + 4 * g]);
+          s[js] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, s[js], 0, 0, 0);
+          s[js] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, s[js], 0, 0, 0);
+          s[js] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, s[js], 0, 0, 0);
+          s[js] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, s[js], 0, 0, 0);
+        }
+      }
+    }
+
+    // selection on the accumulators: s[js][r] is (j = jr + r, i = my_i)
+#pragma unroll
+    for (int js = 0; js < 4; ++js) {
+      const int jr = j0 + js * 16 + 4 * g;
+      const mmd_f4 n_j = *reinterpret_cast<const mmd_f4*>(norms_r + jr);
+      knn_key cand[4];
+      int n_mine = 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float d2 = fmaxf(n_i + n_j[r] - 2.0f * s[js][r], 0.0f);
+        const knn_key key =
+            ((knn_key)(__float_as_uint(d2) & 0x7fffffffu) << 32) | (unsigned)(jr + r);
+        const bool keep = i_ok && jr + r < j_end && jr + r != self_j && key < tau;
+        cand[r] = keep ? key : KNN_INF_KEY;
+        n_mine += keep ? 1 : 0;
+      }
+      if (__ballot(n_mine > 0) != 0ull) {  // rarely, past the first tiles
+        // counts of the row's four lanes, lower g first
+        const int c0 = __shfl(n_mine, h), c1 = __shfl(n_mine, h + 16);
+        const int c2 = __shfl(n_mine, h + 32), c3 = __shfl(n_mine, h + 48);
+        const int added = c0 + c1 + c2 + c3;  // <= 16
+        // rows whose pending area cannot take this step's keys are sorted
+        // first (their survivors were tested against the older, larger tau:
+        // more than needed, never fewer)
+        unsigned todo =
+            (unsigned)(__ballot(pending + added > KNN_PENDING) & 0xffffull);
+        while (todo) {  // uniform
+          const int row = __ffs(todo) - 1;
+          todo &= todo - 1;
+          const knn_key t =
+              knn_flush_row(wave_keys + row * KNN_SLOTS, __shfl(pending, row), k, lane);
+          if (h == row) { tau = t; pending = 0; }
+        }
+        int at = KNN_MAX_K + pending +
+                 (g > 0 ? c0 : 0) + (g > 1 ? c1 : 0) + (g > 2 ? c2 : 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (cand[r] != KNN_INF_KEY) my_keys[at++] = cand[r];
+        pending += added;  // <= KNN_PENDING
+        knn_wave_sync();
+      }
+    }
+  }
+
+  // what is still pending, then the block's sorted lists
+  unsigned todo = (unsigned)(__ballot(pending > 0) & 0xffffull);
+  while (todo) {
+    const int row = __ffs(todo) - 1;
+    todo &= todo - 1;
+    knn_flush_row(wave_keys + row * KNN_SLOTS, __shfl(pending, row), k, lane);
+  }
+  knn_wave_sync();
+  for (int e = lane; e < 16 * k; e += 64) {
+    const int row = e / k, slot = e - row * k;
+    const int gi = i_base + wave * 16 + row;
+    if (gi < B && gi < row0 + rows)
+      part[((size_t)blockIdx.y * rows + (gi - row0)) * k + slot] =
+          wave_keys[row * KNN_SLOTS + slot];
+  }
+}
+
+// One wave per row: merges the splits' sorted lists part[s][row][0 .. k) into
+// the k smallest keys. A lane owns the lists s = lane, lane + 64, ... (at
+// most four) and offers the smallest of their heads; the wave takes the
+// smallest offer k times. Keys of real pairs are unique; only +inf repeats.
+MMD_NO_PACKED_F32 __global__ __launch_bounds__(KNN_BLOCK) void knn_merge_kernel(
+    const knn_key* __restrict__ part, float* __restrict__ d2,
+    int* __restrict__ idx, int splits, int rows, int k)
+{
+  const int lane = threadIdx.x & 63;
+  const int row = (int)blockIdx.x * (KNN_BLOCK / 64) + (threadIdx.x >> 6);
+  if (row >= rows) return;  // a whole wave
+  int head[KNN_MAX_SPLITS / 64] = {0, 0, 0, 0};
+  for (int t = 0; t < k; ++t) {
+    knn_key best = KNN_INF_KEY;
+    int from = -1;
+#pragma unroll
+    for (int q = 0; q < KNN_MAX_SPLITS / 64; ++q) {
+      const int s = lane + 64 * q;
+      if (s < splits && head[q] < k) {
+        const knn_key v = part[((size_t)s * rows + row) * k + head[q]];
+        if (v < best) { best = v; from = q; }
+      }
+    }
+    knn_key low = best;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const knn_key o = __shfl_xor(low, m);
+      low = o < low ? o : low;
+    }
+    if (low != KNN_INF_KEY && best == low) {  // one lane: the key is unique
+#pragma unroll
+      for (int q = 0; q < KNN_MAX_SPLITS / 64; ++q)
+        if (q == from) head[q] += 1;
+    }
+    if (lane == 0) {
+      d2[(size_t)row * k + t] = __uint_as_float((unsigned)(low >> 32));
+      idx[(size_t)row * k + t] = (int)(unsigned)(low & 0xffffffffull);
+    }
+  }
+}
+
+// The k nearest reference rows of batch rows [row_begin, row_begin +
+// row_count): (d2 f32[row_count, k], idx i32[row_count, k]) ascending in
+// (d2, j). z_batch f32[B, Dp] and z_ref f32[M, Dp] with D zero-padded to a
+// multiple of 4, norms the squared row norms. exclude_self leaves out the
+// pair j == i (global row numbers; both sides must then have as many rows).
+std::vector<torch::Tensor> knn_topk(torch::Tensor z_batch, torch::Tensor z_ref,
+                                    torch::Tensor norms_batch, torch::Tensor norms_ref,
+                                    int64_t k, bool exclude_self,
+                                    int64_t cols_per_block, int64_t row_begin,
+                                    int64_t row_count)
+{
+  TORCH_CHECK(z_batch.is_cuda() && z_batch.scalar_type() == torch::kFloat32 &&
+              z_batch.dim() == 2 && z_batch.is_contiguous(),
+              "z_batch must be a contiguous f32[B, Dp] GPU tensor");
+  TORCH_CHECK(z_ref.is_cuda() && z_ref.device() == z_batch.device() &&
+              z_ref.scalar_type() == torch::kFloat32 && z_ref.dim() == 2 &&
+              z_ref.is_contiguous() && z_ref.size(1) == z_batch.size(1),
+              "z_ref must be a contiguous f32[M, Dp] tensor on z_batch's GPU");
+  const int64_t B = z_batch.size(0), M = z_ref.size(0), Dp = z_batch.size(1);
+  TORCH_CHECK(B >= 1 && B <= KNN_MAX_ROWS, "batch rows out of range: ", B);
+  TORCH_CHECK(M >= 1 && M <= KNN_MAX_ROWS, "reference rows out of range: ", M);
+  TORCH_CHECK(Dp >= 4 && Dp % 4 == 0 && Dp <= KNN_MAX_DP,
+              "Dp must be a multiple of 4 in [4, ", KNN_MAX_DP, "]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(z_batch.data_ptr<float>()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(z_ref.data_ptr<float>()) % 16 == 0,
+              "z_batch and z_ref must be 16-byte aligned (rows are read as float4)");
+  TORCH_CHECK(norms_batch.is_cuda() && norms_batch.device() == z_batch.device() &&
+              norms_batch.scalar_type() == torch::kFloat32 && norms_batch.dim() == 1 &&
+              norms_batch.size(0) == B && norms_batch.is_contiguous(),
+              "norms_batch must be a contiguous f32[B] tensor on z_batch's GPU");
+  TORCH_CHECK(norms_ref.is_cuda() && norms_ref.device() == z_batch.device() &&
+              norms_ref.scalar_type() == torch::kFloat32 && norms_ref.dim() == 1 &&
+              norms_ref.size(0) == M && norms_ref.is_contiguous(),
+              "norms_ref must be a contiguous f32[M] tensor on z_batch's GPU");
+  TORCH_CHECK(!exclude_self || B == M,
+              "exclude_self needs the same rows on both sides");
+  TORCH_CHECK(k >= 1 && k <= KNN_MAX_K && k <= M - (exclude_self ? 1 : 0),
+              "k must be in [1, ", KNN_MAX_K, "] and at most the number of "
+              "reference rows a batch row can take");
+  TORCH_CHECK(cols_per_block >= KNN_TILE && cols_per_block % KNN_TILE == 0,
+              "cols_per_block must be a positive multiple of ", KNN_TILE);
+  if (row_count < 0) row_count = B - row_begin;
+  TORCH_CHECK(row_begin >= 0 && row_begin % KNN_TILE == 0 && row_count >= 1 &&
+              row_begin + row_count <= B,
+              "row slice must start on a tile and lie inside [0, B)");
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)z_batch.get_device());
+  const int64_t Mp = (M + KNN_TILE - 1) / KNN_TILE * KNN_TILE;
+  const int64_t splits = (M + cols_per_block - 1) / cols_per_block;  // <= 256
+  // the kernel reads whole float4s of the reference norms unchecked
+  auto norms_p = torch::zeros({Mp}, norms_ref.options());
+  norms_p.slice(0, 0, M).copy_(norms_ref);
+  auto part = torch::empty({splits, row_count, k}, z_batch.options().dtype(torch::kInt64));
+  auto d2 = torch::empty({row_count, k}, z_batch.options());
+  auto idx = torch::empty({row_count, k}, z_batch.options().dtype(torch::kInt32));
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(knn_topk_kernel,
+      dim3((unsigned)((row_count + KNN_TILE - 1) / KNN_TILE), (unsigned)splits),
+      dim3(KNN_BLOCK), 0, stream,
+      z_batch.data_ptr<float>(), z_ref.data_ptr<float>(),
+      norms_batch.data_ptr<float>(), norms_p.data_ptr<float>(),
+      reinterpret_cast<knn_key*>(part.data_ptr<int64_t>()), (int)B, (int)M, (int)Dp,
+      (int)k, (int)cols_per_block, (int)row_begin, (int)row_count,
+      exclude_self ? 1 : 0);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(knn_merge_kernel,
+      dim3((unsigned)((row_count + KNN_BLOCK / 64 - 1) / (KNN_BLOCK / 64))),
+      dim3(KNN_BLOCK), 0, stream,
+      reinterpret_cast<const knn_key*>(part.data_ptr<int64_t>()),
+      d2.data_ptr<float>(), idx.data_ptr<int>(), (int)splits, (int)row_count, (int)k);
+  HIP_CHECK(hipGetLastError());
+  return {d2, idx};
+}
+
+// ---------------------------------------------------------------------------
 // ScoreSession — one replica's resident GPU state + a single-call scoring
 // path. Owns the model buffers in HBM, a private HIP stream, device
 // workspace and pinned staging, so one Python call per request performs:
@@ -5812,6 +6156,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cols_per_block"), py::arg("row_begin") = 0,
         py::arg("row_count") = -1);
   m.attr("MMD_TILE") = py::int_(MMD_TILE);
+  m.def("knn_topk", &knn_topk,
+        "k nearest reference rows per batch row -> (d2 f32[rows, k], idx "
+        "i32[rows, k]): distance GEMM on the matrix cores fused with a "
+        "running top-k, no distance matrix (gfx950)",
+        py::arg("z_batch"), py::arg("z_ref"), py::arg("norms_batch"),
+        py::arg("norms_ref"), py::arg("k"), py::arg("exclude_self"),
+        py::arg("cols_per_block"), py::arg("row_begin") = 0,
+        py::arg("row_count") = -1);
+  m.attr("KNN_TILE") = py::int_(KNN_TILE);
+  m.attr("KNN_MAX_K") = py::int_(KNN_MAX_K);
   m.def("encode_records", &encode_records,
         "Native request encoder: list[dict] -> (codes i16[B,9], nums f32[B,14])");
   m.def("encode_json", &encode_json,
