@@ -13,6 +13,7 @@ Replaces the reference's Databricks bundle + GitHub Actions + Bicep pipeline
     python -m creditcore importance --model-directory ./model --data labelled.csv --out imp.json
     python -m creditcore drift-mmd --model-directory ./model --data batch.csv [--reference ref.csv]
     python -m creditcore outlier-knn --model-directory ./model --data batch.csv [--k 10] --out out.json
+    python -m creditcore anchors --model-directory ./model --data rows.csv --out anchors.json
 """
 
 from __future__ import annotations
@@ -502,6 +503,49 @@ def _cmd_outlier_knn(argv):
         print(json.dumps(doc))
 
 
+def _cmd_anchors(argv):
+    """Offline anchor rules of CSV rows under a packaged model
+    (ScoringEngine.anchors)."""
+    p = argparse.ArgumentParser(prog="creditcore anchors")
+    p.add_argument("--model-directory", default="./model")
+    p.add_argument("--data", required=True,
+                   help="CSV rows to explain (the train --data schema); at most 1024 rows")
+    p.add_argument("--sample", default=None,
+                   help="CSV sample of at most 1024 rows (default: the model's packed sample)")
+    p.add_argument("--precision-threshold", type=float, default=0.95)
+    p.add_argument("--beam-size", type=int, default=2)
+    p.add_argument("--max-anchor-size", type=int, default=6)
+    p.add_argument("--disc-perc", default="25,50,75",
+                   help="comma-separated percentiles that cut numeric features into intervals")
+    p.add_argument("--threshold", type=float, default=0.5)
+    p.add_argument("--device", default="auto")
+    p.add_argument("--out", default=None)
+    a = p.parse_args(argv)
+    import pandas as pd
+
+    from .engine import load_engine
+
+    eng = load_engine(a.model_directory, device=a.device)
+    doc = eng.anchors_records(
+        pd.read_csv(a.data),
+        sample=pd.read_csv(a.sample) if a.sample else None,
+        precision_threshold=a.precision_threshold,
+        beam_size=a.beam_size,
+        max_anchor_size=a.max_anchor_size,
+        disc_perc=[float(q) for q in a.disc_perc.split(",")],
+        threshold=a.threshold,
+    )
+    doc["device"] = eng.device
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(doc, f)
+        print(json.dumps({"out": a.out, "rows": len(doc["rows"]),
+                          "met": sum(r["met"] for r in doc["rows"]),
+                          "sample_rows": doc["sample_rows"], "device": eng.device}))
+    else:
+        print(json.dumps(doc))
+
+
 def _cmd_generate_data(argv):
     """Write a UCI-shaped synthetic CSV (the reference's curated.csv analog,
     reference databricks/data/; the real UCI CSV is not available offline)."""
@@ -542,6 +586,7 @@ def main():
         "importance": _cmd_importance,
         "drift-mmd": _cmd_drift_mmd,
         "outlier-knn": _cmd_outlier_knn,
+        "anchors": _cmd_anchors,
     }
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         print(f"usage: python -m creditcore {{{'|'.join(cmds)}}} [args]", file=sys.stderr)

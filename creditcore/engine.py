@@ -217,6 +217,21 @@ class ScoringEngine:
     # shape). The largest call the caps allow (1024 rows x 14 columns =
     # 14,336 jobs) runs as four launches.
     CF_LAUNCH_JOBS = 4096
+    # anchors: most (mask, sample row) pairs of one forest_anchor launch (a
+    # mask is one candidate anchor of one row, a pair one composite row's sum
+    # over the whole forest, shared with the other masks of its chunk); a
+    # search level above it runs as several launches over row ranges. Sized
+    # like PDP_LAUNCH_PAIRS: the largest measured pair count whose launch on
+    # the flagship forest (RF 500 x depth 16, level-1 candidate lists, 23
+    # masks per row, on the 256-row sample) is no longer than 1.25 x the
+    # method="shap" launch at SHAP_MAX_ROWS measured in the same run:
+    # forest_shap at 1024 rows 60.09 ms (bound 75.11 ms), forest_anchor at
+    # 64 rows x 23 masks x 256 = 376,832 pairs 62.04 ms (128 rows:
+    # 113.25 ms, over the bound) on an MI355X,
+    # bench/anchor_micro.py, profiles/bench_results/anchor_micro.txt. A level
+    # of the largest call the caps allow (1024 rows x 92 masks x 1024 sample
+    # rows, 96 M pairs) runs as 256 launches.
+    ANCHOR_LAUNCH_PAIRS = 376832
     # mmd_drift: most pooled rows i (64-row tiles) of one mmd_perm launch; a
     # call above it runs as several launches over row slices. Sized like
     # ISHAP_MAX_PAIRS: the launch at the caps (n = m = 16384, N = 32768
@@ -1336,6 +1351,170 @@ class ScoringEngine:
                 return gpu.forest_sweep(rows[0], rows[1], m, sw, jb, cut, want_curves)
 
         return run
+
+    # -------------------------------------------------------------- anchors
+    def anchors(
+        self,
+        codes: np.ndarray,
+        nums: np.ndarray,
+        sample=None,
+        precision_threshold: float = 0.95,
+        beam_size: int = 2,
+        max_anchor_size: int = 6,
+        disc_perc=(25, 50, 75),
+        threshold: float = 0.5,
+    ) -> dict:
+        """Anchor rules (alibi's ``AnchorTabular``): per row a small set of
+        predicates on its own features, ``feature == category`` or ``lo <
+        value <= hi`` (the row's interval among the sample column's
+        ``disc_perc`` quantile edges), under which the classifier keeps the
+        row's decision ``probability > threshold`` for at least
+        ``precision_threshold`` of the sample rows, whatever their other
+        features are. creditcore/anchors.py holds the definition: precision
+        and coverage are exact on the sample, and a deterministic beam search
+        (``beam_size`` at most 4, anchors of at most ``max_anchor_size``
+        predicates) returns the widest anchor that reaches the threshold.
+
+        ``sample`` defaults to the pack's background sample
+        (ExplainUnavailable without one); ``(codes, nums)`` of up to 1,024
+        rows overrides it. Each search level is one forest_anchor launch for
+        all rows still searching (cpu_ref.forest_anchor_cpu on a CPU engine),
+        cut at ANCHOR_LAUNCH_PAIRS. Returns ``{"rows", "precision_threshold",
+        "beam_size", "sample_rows"}``; a row holds ``anchor`` (one entry per
+        predicate: ``feature`` and ``category``, or ``low`` / ``high`` with
+        None for an open end), ``names``, ``precision``, ``coverage``, ``met``
+        (False: ``max_anchor_size`` ended the search, the best-precision
+        anchor of the last level is returned), ``decision`` and
+        ``probability``. The scoring session is not touched. Caps
+        (creditcore/anchors.py) raise ExplainTooLarge."""
+        from . import anchors as an
+        from . import counterfactual as cf
+        from .pdp import finalize
+
+        p = self.packed
+        try:
+            prec, beam, max_size, perc = an.check_args(
+                precision_threshold, beam_size, max_anchor_size, disc_perc
+            )
+        except an.AnchorTooLarge as e:
+            raise ExplainTooLarge(str(e)) from None
+        thr = cf.check_threshold(threshold)
+        codes = np.ascontiguousarray(codes, dtype=np.int16)
+        nums = np.ascontiguousarray(nums, dtype=np.float32)
+        r = len(codes)
+        if codes.shape != (r, N_CAT) or nums.shape != (r, N_NUM):
+            raise ValueError(f"rows must be (codes [R, {N_CAT}], nums [R, {N_NUM}])")
+        if r < 1:
+            raise ValueError("anchors needs at least one row")
+        if r > an.ANCHOR_MAX_ROWS:
+            raise ExplainTooLarge(f"anchors is capped at {an.ANCHOR_MAX_ROWS} rows per call (got {r})")
+        if sample is None:
+            if p.bg_codes is None or p.bg_nums is None:
+                raise ExplainUnavailable(
+                    "model was packed without a background sample; re-train and "
+                    "re-pack, or pass sample=(codes, nums)"
+                )
+            sample = (p.bg_codes, p.bg_nums)
+        bg_codes = np.ascontiguousarray(sample[0], dtype=np.int16)
+        bg_nums = np.ascontiguousarray(sample[1], dtype=np.float32)
+        s = len(bg_codes)
+        if bg_codes.shape != (s, N_CAT) or bg_nums.shape != (s, N_NUM) or s < 1:
+            raise ValueError(f"sample must be (codes [S, {N_CAT}], nums [S, {N_NUM}]), S >= 1")
+        if s > an.ANCHOR_MAX_SAMPLE:
+            raise ExplainTooLarge(f"the sample is capped at {an.ANCHOR_MAX_SAMPLE} rows (got {s})")
+        cut = cf.raw_cut(p, thr)
+        nums_imp = cpu_ref.impute_nums(p, nums)
+        bg_imp = cpu_ref.impute_nums(p, bg_nums)
+        edges = an.disc_edges(bg_imp, perc)
+        sat = an.sat_table(codes, nums_imp, bg_codes, bg_imp, edges)
+        # the rows' own decisions: the scorer's tree-order sums, on the host
+        # for both engines (R walks of the forest against R x S x masks)
+        own_raw = cpu_ref.forest_raw_cpu(p, codes, nums_imp, tree_order=True)
+        with self._explain_lock:
+            if self.device == "cuda":
+                launch = self._anchor_gpu(codes, nums, bg_codes, bg_nums, sat, cut)
+            else:
+                def launch(a, b, masks, off):
+                    return cpu_ref.forest_anchor_cpu(
+                        p, codes[a:b], nums_imp[a:b], bg_codes, bg_imp, sat[a:b], masks, off, cut
+                    )[0]
+
+            def run(masks: np.ndarray, mask_off: np.ndarray) -> np.ndarray:
+                parts = [
+                    launch(a, b, masks[mask_off[a] : mask_off[b]], mask_off[a : b + 1] - mask_off[a])
+                    for a, b in an.launch_slices(mask_off, s, int(self.ANCHOR_LAUNCH_PAIRS))
+                ]
+                return np.concatenate(parts)
+
+            found = an.search(run, sat, own_raw > cut, prec, beam, max_size)
+        prob = finalize(
+            own_raw, int(getattr(p, "cls_kind", 0)), float(p.cls_bias), int(p.cls_n_trees),
+            "probability",
+        )
+        rows = []
+        for i, (mask, hits, covered, met) in enumerate(found):
+            entries, names = an.describe(mask, codes[i], nums_imp[i], edges, p.vocabs)
+            rows.append(
+                {
+                    "anchor": entries,
+                    "names": names,
+                    "precision": hits / s,
+                    "coverage": covered / s,
+                    "met": met,
+                    "decision": int(own_raw[i] > cut),
+                    "probability": float(prob[i]),
+                }
+            )
+        return {
+            "rows": rows,
+            "precision_threshold": prec,
+            "beam_size": beam,
+            "sample_rows": s,
+        }
+
+    def _anchor_gpu(self, codes, nums, bg_codes, bg_nums, sat: np.ndarray, cut: float):
+        """One-launch runner of forest_anchor on the device (a row range and
+        its candidate lists in, numpy counts out); the caller holds
+        _explain_lock. Rows, sample and the sat table are uploaded here, once
+        per call; a level uploads only its masks."""
+        import torch
+
+        ext = self._gpu["ext"]
+        dev = torch.device("cuda", self.device_index)
+        m = self._forest_dev()
+        up = [
+            torch.from_numpy(a).to(dev)
+            for a in (codes, nums, bg_codes, bg_nums, np.ascontiguousarray(sat).view(np.int32))
+        ]
+
+        def run(a: int, b: int, masks: np.ndarray, mask_off: np.ndarray) -> np.ndarray:
+            with torch.cuda.device(dev):
+                counts, _ = ext.forest_anchor(
+                    up[0][a:b],
+                    up[1][a:b],
+                    up[2],
+                    up[3],
+                    m["cls_nodes"],
+                    m["cls_off"],
+                    m["feat_col"],
+                    m["feat_code"],
+                    m["medians"],
+                    up[4][a:b],
+                    torch.from_numpy(np.ascontiguousarray(masks, dtype=np.uint32).view(np.int32)),
+                    torch.from_numpy(np.ascontiguousarray(mask_off, dtype=np.int32)),
+                    float(cut),
+                )
+                return counts.cpu().numpy()  # the D2H copy synchronizes
+
+        return run
+
+    def anchors_records(self, records, sample=None, **kw) -> dict:
+        """anchors on a request body (list of dicts / DataFrame); ``sample``
+        likewise, encoded with the same vocabulary."""
+        codes, nums = encode_batch(records, self.packed.vocabs)
+        if sample is not None:
+            sample = encode_batch(sample, self.packed.vocabs)
+        return self.anchors(codes, nums, sample=sample, **kw)
 
     # ------------------------------------------------------------ MMD drift
     def mmd_drift(

@@ -253,6 +253,64 @@ def forest_permute_cpu(
     return out
 
 
+def forest_anchor_cpu(
+    packed: PackedModel,
+    codes: np.ndarray,
+    nums_imp: np.ndarray,
+    bg_codes: np.ndarray,
+    bg_nums_imp: np.ndarray,
+    sat: np.ndarray,
+    masks: np.ndarray,
+    mask_off: np.ndarray,
+    cut: float,
+    want_sums: bool = False,
+    max_pairs: int = 1 << 21,
+):
+    """Anchor counts, the reference (and the definition) of
+    forest_anchor_kernel: ``(counts i32[M], sums f64[M, S] or None)``. Row i
+    of the (imputed) rows to explain has the candidate anchors
+    ``masks[mask_off[i]:mask_off[i + 1]]``, each a u32 set of schema players
+    (0..N_CAT-1 categorical, N_CAT.. numeric). The composite of row i, mask A
+    and sample row b is the (imputed) sample row with every player of
+    ``A & ~sat[i, b]`` replaced by row i's value; ``sums[m, b]`` is its
+    tree-order raw classifier sum and ``counts[m]`` the number of sample rows
+    with ``sums[m, b] > cut``. Deliberately the dumb version: every composite
+    row is written out and summed by the scorer's own traversal
+    (forest_raw_cpu with ``tree_order``), at most ``max_pairs`` (row, tree)
+    pairs per traversal call."""
+    codes = np.ascontiguousarray(codes, dtype=np.int16)
+    nums_imp = np.ascontiguousarray(nums_imp, dtype=np.float32)
+    bg_codes = np.ascontiguousarray(bg_codes, dtype=np.int16)
+    bg_nums_imp = np.ascontiguousarray(bg_nums_imp, dtype=np.float32)
+    sat = np.asarray(sat).astype(np.uint32, copy=False)
+    masks = np.asarray(masks).astype(np.uint32, copy=False).reshape(-1)
+    mask_off = np.asarray(mask_off, dtype=np.int64).reshape(-1)
+    r, s = len(codes), len(bg_codes)
+    if r < 1 or s < 1:
+        raise ValueError("forest_anchor needs at least one row and one sample row")
+    if sat.shape != (r, s):
+        raise ValueError(f"sat must be [{r}, {s}]")
+    if len(mask_off) != r + 1 or mask_off[0] != 0 or mask_off[-1] != len(masks):
+        raise ValueError("mask_off does not span masks")
+    if (np.diff(mask_off) < 0).any() or (masks >> np.uint32(N_CAT + N_NUM)).any():
+        raise ValueError("mask_off must not decrease; masks hold players below N_CAT + N_NUM")
+    sums = np.empty((len(masks), s), dtype=np.float64)
+    step = max(1, max_pairs // max(1, s * packed.cls_n_trees))
+    player_bit = np.uint32(1) << np.arange(N_CAT + N_NUM, dtype=np.uint32)
+    for i in range(r):
+        for a in range(mask_off[i], mask_off[i + 1], step):
+            chunk = masks[a : min(a + step, mask_off[i + 1])]
+            # [n, S, players]: whether the composite takes row i's value
+            take = ((chunk[:, None] & ~sat[i][None, :])[:, :, None] & player_bit) != 0
+            c = np.where(take[:, :, :N_CAT], codes[i], bg_codes[None, :, :])
+            x = np.where(take[:, :, N_CAT:], nums_imp[i], bg_nums_imp[None, :, :])
+            sums[a : a + len(chunk)] = forest_raw_cpu(
+                packed, c.reshape(-1, N_CAT), x.reshape(-1, N_NUM), tree_order=True
+            ).reshape(len(chunk), s)
+    counts = (sums > cut).sum(axis=1).astype(np.int32)
+    return counts, (sums if want_sums else None)
+
+
 def forest_sweep_cpu(
     packed: PackedModel,
     codes: np.ndarray,

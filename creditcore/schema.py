@@ -334,6 +334,58 @@ class CounterfactualOutput(BaseModel):
     rows: list[CounterfactualRow]
 
 
+class AnchorsRequest(BaseModel):
+    """POST /explain/anchors request: the records as /explain takes them, the
+    share of sample rows that must keep the record's decision under the
+    anchor, the beam width and size limit of the search, the percentiles
+    that cut numeric features into intervals and the decision threshold on
+    the predicted probability."""
+
+    records: list[dict]
+    precision_threshold: float = 0.95
+    beam_size: int = 2
+    max_anchor_size: int = 6
+    disc_perc: list[float] = [25.0, 50.0, 75.0]
+    threshold: float = 0.5
+
+    model_config = ConfigDict(extra="ignore")
+
+
+class AnchorPredicate(BaseModel):
+    """One predicate of an anchor: ``feature == category``, or ``low <
+    feature <= high`` with null for an open end."""
+
+    feature: str
+    category: str | None = None
+    low: float | None = None
+    high: float | None = None
+
+
+class AnchorRow(BaseModel):
+    """``precision``: the share of sample rows that keep the record's
+    ``decision`` once the anchor's features are set to the record's;
+    ``coverage``: the share of sample rows the anchor applies to; ``met``:
+    whether ``precision`` reached the requested threshold."""
+
+    anchor: list[AnchorPredicate]
+    names: list[str]
+    precision: float
+    coverage: float
+    met: bool
+    decision: int
+    probability: float
+
+
+class AnchorsOutput(BaseModel):
+    """POST /explain/anchors response: one entry per record, exact on the
+    model's ``sample_rows`` background rows."""
+
+    rows: list[AnchorRow]
+    precision_threshold: float
+    beam_size: int
+    sample_rows: int
+
+
 class MmdDriftRequest(BaseModel):
     """POST /drift/mmd request: the records as /score takes them, the number
     of permutations behind the p-value and the seed they are drawn from."""

@@ -40,6 +40,8 @@ from .schema import (
     FEATURES,
     AleOutput,
     AleRequest,
+    AnchorsOutput,
+    AnchorsRequest,
     CounterfactualOutput,
     CounterfactualRequest,
     ExplainOutput,
@@ -894,6 +896,76 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
             raise HTTPException(status_code=500, detail=f"permutation importance failed: {e}")
         for res in out["results"]:
             res["importances"] = res["importances"].tolist()
+        metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
+        return _json_response(out)
+
+    @app.post("/explain/anchors", response_model=AnchorsOutput)
+    async def explain_anchors(req: AnchorsRequest):
+        """Anchor rules for the posted records: per record the widest small
+        set of predicates on its own features under which the classifier
+        keeps its decision for at least ``precision_threshold`` of the
+        model's packed background sample (ScoringEngine.anchors). One attempt
+        on one live replica; bypasses the micro-batcher."""
+        import asyncio
+
+        from .anchors import ANCHOR_MAX_BEAM, ANCHOR_MAX_ROWS
+
+        metrics: Metrics = state["metrics"]
+        engines = state["engines"]
+        pool: ReplicaPool = state["pool"]
+        packed = engines[0].packed
+        if packed.bg_codes is None or packed.bg_nums is None:
+            raise HTTPException(
+                status_code=501,
+                detail="the served model was packed without a background sample; "
+                "re-train and re-pack it to enable /explain/anchors",
+            )
+        if len(req.records) > ANCHOR_MAX_ROWS:
+            raise HTTPException(
+                status_code=413, detail=f"/explain/anchors takes at most {ANCHOR_MAX_ROWS} rows"
+            )
+        if req.beam_size > ANCHOR_MAX_BEAM:
+            raise HTTPException(
+                status_code=413,
+                detail=f"/explain/anchors takes a beam_size of at most {ANCHOR_MAX_BEAM}",
+            )
+        if len(req.records) < 1:
+            raise HTTPException(status_code=422, detail="/explain/anchors needs at least one row")
+        try:
+            codes, nums = encode_batch(req.records, packed.vocabs)
+        except (ValueError, TypeError, KeyError) as e:
+            raise HTTPException(status_code=422, detail=f"bad record: {e}")
+        try:
+            idx = pool.pick()
+        except RuntimeError:
+            metrics.observe_error()
+            raise HTTPException(status_code=503, detail="no healthy replicas")
+        t0 = time.perf_counter()
+
+        def call():
+            return engines[idx].anchors(
+                codes,
+                nums,
+                precision_threshold=req.precision_threshold,
+                beam_size=req.beam_size,
+                max_anchor_size=req.max_anchor_size,
+                disc_perc=req.disc_perc,
+                threshold=req.threshold,
+            )
+
+        try:
+            out = await asyncio.get_running_loop().run_in_executor(None, call)
+            pool.report_ok(idx)
+        except ExplainTooLarge as e:  # the request's fault, not the replica's
+            raise HTTPException(status_code=413, detail=str(e))
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        except ExplainUnavailable as e:
+            raise HTTPException(status_code=501, detail=str(e))
+        except Exception as e:
+            metrics.observe_error()
+            pool.report_fail(idx)
+            raise HTTPException(status_code=500, detail=f"anchors failed: {e}")
         metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
         return _json_response(out)
 

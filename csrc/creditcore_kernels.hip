@@ -1414,6 +1414,198 @@ ALE_NO_PACKED_F32 __global__ __launch_bounds__(PERM_BLOCK) void forest_permute_k
   }
 }
 
+// Anchor rules: per candidate anchor of a row, the number of background sample
+// rows whose COMPOSITE has a raw classifier sum above `cut`. An anchor is a
+// u32 set of schema players (the numbering of forest_whatif_kernel). The
+// composite z(i, A, b) of row i, anchor A and sample row b is the sample row
+// with every player of A & ~sat[i, b] replaced by row i's own (imputed)
+// value; sat[i, b] is the host's set of players whose predicate, taken from
+// row i, sample row b satisfies already (creditcore/anchors.py), and those
+// keep the sample's value. Row i's candidates are masks[mask_off[i] ..
+// mask_off[i + 1]); the host cuts them into jobs {row, first mask, n} of at
+// most ANCHOR_CHUNK = 64 masks.
+//
+// Work split: one-wave blocks, blockIdx.x the job, blockIdx.y striding over
+// the 64-row passes of the sample; thread `tid` owns sample row b0 + tid of a
+// pass and ALL trees, for all masks of the job at once. Row i (imputed), the pass's sample rows (column-major,
+// imputed, own slots only) and has[p], the u64 set of the job's masks that
+// contain player p, are staged in LDS; the thread's sat word is a register.
+//
+// Shared walk. All masks of a job see the same tree and differ only in which
+// players they replace, so a tree is walked once with cursors (node, live),
+// live a u64 set of the job's masks, all of them at the root. At a node on
+// player p the branch is taken under row i's value (gx) and under the sample
+// row's (gb). If p is in sat, or gx == gb, every composite goes gb. Otherwise
+// live & has[p] goes gx and live & ~has[p] goes gb; an empty side is not
+// walked, and of two live sides one is pushed on the thread's stack. After a
+// split live is uniform in p, so a path splits at most once per player and
+// the stack never holds more than N_SRC entries of 12 B (LDS, own slots).
+// At a leaf its value is added, as f64, to the accumulator of every mask in
+// live (64 f64 per thread in LDS, own slots). The leaves of a tree partition
+// the masks, so every accumulator takes exactly one add per tree, tree after
+// tree: the sum is the tree-order sum of walking the composite row on its
+// own, bit for bit (forest_whatif_kernel wherever a composite is at most two
+// overrides). One tree is in flight per thread; that keeps the order trivially.
+//
+// Counts: after the last tree each accumulator is compared with `cut`, the
+// wave's votes are counted with one ballot per mask, and lane m keeps mask
+// m's count over the block's passes: a plain store at the end into the
+// block's own row of counts[gridDim.y, M] (the launcher adds the rows: counts
+// are integers), no atomics, no pre-zeroed output. `sums` (tests, the
+// micro-benchmark) may be null.
+//
+// Bounds by construction (the note on forest_sweep_kernel): a tree outside
+// the node table is skipped, a node index is compared unsigned against the
+// tree's size before every load, a feature index outside the table reads as a
+// leaf, players and the job's row and mask range are clamped, the walk of a
+// tree takes at most `size` steps over all of its cursors, and a push checks
+// the stack's N_SRC slots (a full stack, bad tables only, drops that side).
+#define ANCHOR_BLOCK 64
+#define ANCHOR_CHUNK 64
+#define ANCHOR_STACK N_SRC
+
+__global__ __launch_bounds__(ANCHOR_BLOCK) void forest_anchor_kernel(
+    const short* __restrict__ codes,     // [R, N_CAT] the rows to explain
+    const float* __restrict__ nums,      // [R, N_NUM], NaNs not yet imputed
+    const short* __restrict__ bg_codes,  // [S, N_CAT] the sample
+    const float* __restrict__ bg_nums,   // [S, N_NUM], NaNs not yet imputed
+    const float* __restrict__ medians,   // [N_NUM]
+    const int4* __restrict__ nodes,      // [n_nodes] {feat, bits, left, right}
+    const int* __restrict__ tree_off,    // [T+1]
+    int n_trees,
+    unsigned n_nodes,
+    const int* __restrict__ feat_col,    // [F]
+    const int* __restrict__ feat_code,   // [F]
+    unsigned n_feat,
+    const unsigned* __restrict__ sat,    // [R, S]
+    const unsigned* __restrict__ masks,  // [M]
+    const int4* __restrict__ jobs,       // [J] {row, first mask, n, 0}
+    int n_rows,
+    int n_bg,
+    int n_masks,                         // M >= 1
+    double cut,
+    int* __restrict__ counts,            // [gridDim.y, M]; every entry is written
+    double* __restrict__ sums)           // [M, S] or null; all written
+{
+  typedef unsigned long long u64;
+  __shared__ double s_acc[ANCHOR_CHUNK * ANCHOR_BLOCK];
+  __shared__ u64 s_stk_live[ANCHOR_STACK * ANCHOR_BLOCK];
+  __shared__ int s_stk_node[ANCHOR_STACK * ANCHOR_BLOCK];
+  __shared__ u64 s_has[N_SRC];
+  __shared__ short s_codes[N_CAT * ANCHOR_BLOCK];
+  __shared__ float s_nums[N_NUM * ANCHOR_BLOCK];
+  __shared__ short s_xc[N_CAT];
+  __shared__ float s_xn[N_NUM];
+
+  const int tid = threadIdx.x;
+  const int4 job = jobs[blockIdx.x];
+  const int row = min(max(job.x, 0), n_rows - 1);
+  const int m0 = min(max(job.y, 0), n_masks - 1);
+  const int nm = min(max(job.z, 0), min(ANCHOR_CHUNK, n_masks - m0));
+
+  // block-uniform tables: row i, imputed, and the chunk's per-player sets
+  if (tid < N_CAT) {
+    s_xc[tid] = codes[(size_t)row * N_CAT + tid];
+  } else if (tid < N_SRC) {
+    const float v = nums[(size_t)row * N_NUM + (tid - N_CAT)];
+    s_xn[tid - N_CAT] = isnan(v) ? medians[tid - N_CAT] : v;
+  }
+  if (tid < N_SRC) {
+    u64 h = 0;
+    for (int k = 0; k < nm; ++k) h |= (u64)((masks[m0 + k] >> tid) & 1u) << k;
+    s_has[tid] = h;
+  }
+  __syncthreads();
+
+  const u64 all = (nm >= 64) ? ~0ull : ((1ull << nm) - 1ull);
+  int my_count = 0;  // lane m: mask m0 + m
+
+  for (int b0 = blockIdx.y * ANCHOR_BLOCK; b0 < n_bg; b0 += gridDim.y * ANCHOR_BLOCK) {
+    const int b = b0 + tid;
+    const bool active = b < n_bg;  // idle lanes still vote below
+    if (active) {
+#pragma unroll
+      for (int c = 0; c < N_CAT; ++c)
+        s_codes[c * ANCHOR_BLOCK + tid] = bg_codes[(size_t)b * N_CAT + c];
+#pragma unroll
+      for (int c = 0; c < N_NUM; ++c) {
+        const float v = bg_nums[(size_t)b * N_NUM + c];
+        s_nums[c * ANCHOR_BLOCK + tid] = isnan(v) ? medians[c] : v;
+      }
+      const unsigned sat_w = sat[(size_t)row * n_bg + b];
+      for (int m = 0; m < nm; ++m) s_acc[m * ANCHOR_BLOCK + tid] = 0.0;
+
+      for (int t = 0; t < n_trees; ++t) {
+        const int base = tree_off[t];
+        const int sz = tree_off[t + 1] - base;
+        if (base < 0 || sz <= 0 || (unsigned)base + (unsigned)sz > n_nodes) continue;
+        const unsigned size = (unsigned)sz;
+
+        int4 nd = nodes[base];
+        u64 live = all;
+        int sp = 0;
+        for (unsigned it = 0; it < size; ++it) {
+          if ((unsigned)nd.x >= n_feat) {  // a leaf: one add per live mask
+            const double v = (double)__int_as_float(nd.y);
+            for (u64 l = live; l != 0ull; l &= l - 1ull)
+              s_acc[(__ffsll((long long)l) - 1) * ANCHOR_BLOCK + tid] += v;
+            if (sp == 0) break;
+            --sp;
+            live = s_stk_live[sp * ANCHOR_BLOCK + tid];
+            nd = ale_load(nodes, base, size, s_stk_node[sp * ANCHOR_BLOCK + tid]);
+            continue;
+          }
+          const int fcol = feat_col[nd.x];
+          const int code = feat_code[nd.x];
+          int p;
+          float vx, vb;
+          if (code >= 0) {
+            p = (int)min((unsigned)fcol, (unsigned)(N_CAT - 1));
+            vx = (s_xc[p] == (short)code) ? 1.0f : 0.0f;
+            vb = (s_codes[p * ANCHOR_BLOCK + tid] == (short)code) ? 1.0f : 0.0f;
+          } else {
+            const int c = (int)min((unsigned)fcol, (unsigned)(N_NUM - 1));
+            p = N_CAT + c;
+            vx = s_xn[c];
+            vb = s_nums[c * ANCHOR_BLOCK + tid];
+          }
+          const float thr = __int_as_float(nd.y);
+          const bool gx = vx <= thr;
+          const bool gb = vb <= thr;
+          int next = gb ? nd.z : nd.w;
+          if (gx != gb && !((sat_w >> p) & 1u)) {
+            const u64 has = s_has[p];
+            const u64 lx = live & has;
+            const u64 lb = live & ~has;
+            if (lx != 0ull) {
+              if (lb != 0ull && sp < ANCHOR_STACK) {
+                s_stk_live[sp * ANCHOR_BLOCK + tid] = lb;
+                s_stk_node[sp * ANCHOR_BLOCK + tid] = next;
+                ++sp;
+              }
+              live = lx;
+              next = gx ? nd.z : nd.w;
+            }
+          }
+          nd = ale_load(nodes, base, size, next);
+        }
+      }
+
+      if (sums != nullptr)
+        for (int m = 0; m < nm; ++m)
+          sums[(size_t)(m0 + m) * n_bg + b] = s_acc[m * ANCHOR_BLOCK + tid];
+    }
+
+    // nm and b0 are block-uniform: every lane of the wave reaches each ballot
+    for (int m = 0; m < nm; ++m) {
+      const bool over = active && s_acc[m * ANCHOR_BLOCK + tid] > cut;
+      const int c = __popcll(__ballot(over));
+      if (tid == m) my_count += c;
+    }
+  }
+  if (tid < nm) counts[(size_t)blockIdx.y * n_masks + m0 + tid] = my_count;
+}
+
 // Exact single-feature sweep for counterfactuals: the raw classifier sum of
 // one row as ONE numeric column moves over the whole real line, every other
 // column held fixed. The sum is piecewise constant in that column; its
@@ -2527,6 +2719,120 @@ torch::Tensor forest_permute(
       perm_dev.data_ptr<int>(), (int)Q, (int)R, out.data_ptr<double>());
   HIP_CHECK(hipGetLastError());
   return out;
+}
+
+// Anchor rules (forest_anchor_kernel): {counts i32[M], sums}. Row i of the R
+// rows to explain has the candidate anchors masks[mask_off[i] ..
+// mask_off[i + 1]) (a list may be empty); counts[m] is the number of the S
+// sample rows whose composite under mask m has a raw classifier sum > cut,
+// and with `want_sums` sums is f64[M, S], those raw sums (an empty tensor
+// otherwise). `sat` is i32[R, S] on the device (bit p: sample row b already
+// satisfies row i's predicate on player p); `masks` (i32[M], bits 0..N_SRC-1)
+// and `mask_off` (i32[R + 1]) are HOST tables: they are checked here, cut
+// into jobs of at most `chunk` <= ANCHOR_CHUNK masks of one row and copied to
+// the device on the caller's stream. A job's masks share one walk per tree
+// and thread, but a job is one block per 64 sample rows, so a launch with few
+// masks needs small jobs to fill the device: `chunk` = 0 picks the smallest
+// chunk that still leaves `block_target` blocks. Stateless like
+// forest_permute; the kernel bounds-checks the forest tables itself.
+std::vector<torch::Tensor> forest_anchor(
+    torch::Tensor codes, torch::Tensor nums,
+    torch::Tensor bg_codes, torch::Tensor bg_nums,
+    torch::Tensor cls_nodes, torch::Tensor cls_off,
+    torch::Tensor feat_col, torch::Tensor feat_code,
+    torch::Tensor medians, torch::Tensor sat,
+    torch::Tensor masks, torch::Tensor mask_off,
+    double cut, bool want_sums, int64_t chunk, int64_t block_target)
+{
+  check_inputs(codes, nums);
+  check_inputs(bg_codes, bg_nums);
+  TORCH_CHECK(chunk >= 0 && chunk <= ANCHOR_CHUNK, "chunk must be in [0, ", ANCHOR_CHUNK, "]");
+  TORCH_CHECK(block_target >= 1 && block_target <= 65535, "bad block_target");
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType st, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == codes.device(), name,
+                " must be on the inputs' GPU");
+    TORCH_CHECK(t.scalar_type() == st && t.is_contiguous(), name,
+                " has the wrong dtype or is not contiguous");
+  };
+  auto on_host = [&](const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(!t.is_cuda() && t.scalar_type() == torch::kInt32 && t.is_contiguous() &&
+                t.dim() == 1, name, " must be a contiguous 1-dimensional host int32 table");
+  };
+  on_dev(nums, torch::kFloat32, "nums");
+  on_dev(bg_codes, torch::kInt16, "bg_codes");
+  on_dev(bg_nums, torch::kFloat32, "bg_nums");
+  on_dev(cls_nodes, torch::kInt32, "cls_nodes");
+  on_dev(cls_off, torch::kInt32, "cls_off");
+  on_dev(feat_col, torch::kInt32, "feat_col");
+  on_dev(feat_code, torch::kInt32, "feat_code");
+  on_dev(medians, torch::kFloat32, "medians");
+  on_dev(sat, torch::kInt32, "sat");
+  on_host(masks, "masks");
+  on_host(mask_off, "mask_off");
+  TORCH_CHECK(cls_nodes.dim() == 2 && cls_nodes.size(1) == 4, "cls_nodes must be [n, 4]");
+  TORCH_CHECK(cls_nodes.size(0) < (int64_t(1) << 31), "too many nodes");
+  TORCH_CHECK(feat_col.numel() == feat_code.numel(), "feat_col/feat_code size mismatch");
+  TORCH_CHECK(medians.numel() == N_NUM, "medians must have N_NUM entries");
+  TORCH_CHECK(cls_off.numel() >= 2, "forest has no trees");
+  TORCH_CHECK(std::isfinite(cut), "cut must be finite");
+
+  const int64_t R = codes.size(0);
+  const int64_t S = bg_codes.size(0);
+  const int64_t M = masks.numel();
+  TORCH_CHECK(R >= 1, "forest_anchor needs at least one row");
+  TORCH_CHECK(S >= 1, "forest_anchor needs at least one sample row");
+  TORCH_CHECK(R < (int64_t(1) << 31) && S < (int64_t(1) << 31) && M < (int64_t(1) << 31),
+              "too many rows, sample rows or masks");
+  TORCH_CHECK(sat.dim() == 2 && sat.size(0) == R && sat.size(1) == S,
+              "sat must be [", R, ", ", S, "] (one word per row and sample row)");
+  TORCH_CHECK(mask_off.numel() == R + 1, "mask_off must have one entry per row and one more");
+  const int* mo = mask_off.data_ptr<int>();
+  const int* mk = masks.data_ptr<int>();
+  TORCH_CHECK(mo[0] == 0 && (int64_t)mo[R] == M, "mask_off does not span masks");
+  for (int64_t i = 0; i < R; ++i)
+    TORCH_CHECK(mo[i + 1] >= mo[i], "mask_off must not decrease");
+  for (int64_t m = 0; m < M; ++m)
+    TORCH_CHECK((unsigned)mk[m] < (1u << N_SRC), "masks[", m, "] holds a player outside [0, ",
+                N_SRC, ")");
+
+  // one block per job and 64-row pass of the sample (up to the grid's limit)
+  const int64_t passes = std::min<int64_t>(ceil_div((int)S, ANCHOR_BLOCK), 65535);
+  if (chunk == 0)
+    chunk = std::max<int64_t>(1, std::min<int64_t>(ANCHOR_CHUNK, M * passes / block_target));
+  // jobs {row, first mask, n, 0}: a row's list, cut every `chunk` masks
+  const int step = (int)chunk;
+  std::vector<int> jb;
+  for (int64_t i = 0; i < R; ++i)
+    for (int a = mo[i]; a < mo[i + 1]; a += step)
+      jb.insert(jb.end(), {(int)i, a, std::min(step, mo[i + 1] - a), 0});
+  const int64_t J = (int64_t)jb.size() / 4;
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)codes.get_device());
+  auto dev = codes.device();
+  auto counts = torch::empty({passes, M}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
+  auto sums = torch::empty({want_sums ? M : 0, S},
+                           torch::TensorOptions().dtype(torch::kFloat64).device(dev));
+  if (J == 0) return {counts.view({-1}), sums};  // every list is empty
+  auto jobs_dev = torch::from_blob(jb.data(), {J, 4}, torch::kInt32).to(dev);
+  auto masks_dev = masks.to(dev);
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  const int T = (int)cls_off.size(0) - 1;
+  hipLaunchKernelGGL(forest_anchor_kernel, dim3((unsigned)J, (unsigned)passes),
+      dim3(ANCHOR_BLOCK), 0, stream,
+      codes.data_ptr<short>(), nums.data_ptr<float>(),
+      bg_codes.data_ptr<short>(), bg_nums.data_ptr<float>(), medians.data_ptr<float>(),
+      reinterpret_cast<const int4*>(cls_nodes.data_ptr<int>()),
+      cls_off.data_ptr<int>(), T, (unsigned)cls_nodes.size(0),
+      feat_col.data_ptr<int>(), feat_code.data_ptr<int>(), (unsigned)feat_col.numel(),
+      reinterpret_cast<const unsigned*>(sat.data_ptr<int>()),
+      reinterpret_cast<const unsigned*>(masks_dev.data_ptr<int>()),
+      reinterpret_cast<const int4*>(jobs_dev.data_ptr<int>()),
+      (int)R, (int)S, (int)M, cut, counts.data_ptr<int>(),
+      want_sums ? sums.data_ptr<double>() : nullptr);
+  HIP_CHECK(hipGetLastError());
+  // a pass's counts are integers: adding the rows is exact in any order
+  return {passes == 1 ? counts.view({M}) : counts.sum(0, false, torch::kInt32), sums};
 }
 
 // Exact single-feature sweep (forest_sweep_kernel + forest_sweep_search_kernel)
@@ -6075,6 +6381,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_target") = 8192);
   m.attr("PERM_ROWS_PER_BLOCK") = py::int_(PERM_BLOCK);
   m.attr("PERM_ILP") = py::int_(PERM_ILP);
+  m.def("forest_anchor", &forest_anchor,
+        "Anchor rules: per candidate anchor (a set of pinned features) of a "
+        "row, the number of sample rows whose composite scores above cut, "
+        "{i32[M], f64[M,S] with want_sums} (one walk of a tree serves all "
+        "candidates of a chunk; gfx950)",
+        py::arg("codes"), py::arg("nums"), py::arg("bg_codes"),
+        py::arg("bg_nums"), py::arg("cls_nodes"), py::arg("cls_off"),
+        py::arg("feat_col"), py::arg("feat_code"), py::arg("medians"),
+        py::arg("sat"), py::arg("masks"), py::arg("mask_off"),
+        py::arg("cut"), py::arg("want_sums") = false, py::arg("chunk") = 0,
+        py::arg("block_target") = 4096);
+  m.attr("ANCHOR_CHUNK") = py::int_(ANCHOR_CHUNK);
   m.def("forest_sweep", &forest_sweep,
         "Exact single-feature sweep: per {row, numeric column} job the raw "
         "forest sum of every threshold interval, searched on the device for "
