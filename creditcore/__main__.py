@@ -14,6 +14,7 @@ Replaces the reference's Databricks bundle + GitHub Actions + Bicep pipeline
     python -m creditcore drift-mmd --model-directory ./model --data batch.csv [--reference ref.csv]
     python -m creditcore outlier-knn --model-directory ./model --data batch.csv [--k 10] --out out.json
     python -m creditcore anchors --model-directory ./model --data rows.csv --out anchors.json
+    python -m creditcore proximity --model-directory ./model --data batch.csv [--k 10] --out out.json
 """
 
 from __future__ import annotations
@@ -503,6 +504,48 @@ def _cmd_outlier_knn(argv):
         print(json.dumps(doc))
 
 
+def _cmd_proximity(argv):
+    """Offline forest proximity of CSV rows under a packaged model
+    (ScoringEngine.proximity)."""
+    p = argparse.ArgumentParser(prog="creditcore proximity")
+    p.add_argument("--model-directory", default="./model")
+    p.add_argument("--data", required=True,
+                   help="CSV batch (the train --data schema); at most 16384 rows")
+    p.add_argument("--reference", default=None,
+                   help="CSV reference sample (default: the model's packed sample)")
+    p.add_argument("--k", type=int, default=10)
+    p.add_argument("--score", choices=("kth", "mean"), default="kth")
+    p.add_argument("--fpr", type=float, default=0.05)
+    p.add_argument("--no-neighbors", action="store_true",
+                   help="leave out each row's k closest reference rows")
+    p.add_argument("--device", default="auto")
+    p.add_argument("--out", default=None)
+    a = p.parse_args(argv)
+    import pandas as pd
+
+    from .engine import load_engine
+
+    eng = load_engine(a.model_directory, device=a.device)
+    doc = eng.proximity_records(
+        pd.read_csv(a.data),
+        reference=pd.read_csv(a.reference) if a.reference else None,
+        k=a.k,
+        score=a.score,
+        fpr=a.fpr,
+        neighbors=not a.no_neighbors,
+    )
+    doc = {key: v.tolist() if hasattr(v, "tolist") else v for key, v in doc.items()}
+    doc["device"] = eng.device
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(doc, f)
+        print(json.dumps({"out": a.out, "n": doc["n"], "n_ref": doc["n_ref"],
+                          "n_trees": doc["n_trees"], "threshold": doc["threshold"],
+                          "outliers": int(sum(doc["is_outlier"])), "device": eng.device}))
+    else:
+        print(json.dumps(doc))
+
+
 def _cmd_anchors(argv):
     """Offline anchor rules of CSV rows under a packaged model
     (ScoringEngine.anchors)."""
@@ -587,6 +630,7 @@ def main():
         "drift-mmd": _cmd_drift_mmd,
         "outlier-knn": _cmd_outlier_knn,
         "anchors": _cmd_anchors,
+        "proximity": _cmd_proximity,
     }
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         print(f"usage: python -m creditcore {{{'|'.join(cmds)}}} [args]", file=sys.stderr)

@@ -252,6 +252,18 @@ class ScoringEngine:
     # launch 2.70 ms on an MI355X. The caps allow no larger call, so today no
     # call is sliced.
     KNN_LAUNCH_ROWS = 16384
+    # proximity: most batch rows (one block each) of one forest_prox_topk
+    # launch; a call above it runs as several launches over row slices. Same
+    # rule: the longest launch the engine issues may take no longer than
+    # 1.25 x the method="shap" launch at SHAP_MAX_ROWS measured in the same
+    # run (bench/prox_micro.py, profiles/bench_results/prox_micro.txt):
+    # forest_shap at 1024 rows 60.39 ms (bound 75.48 ms), forest_prox_topk at
+    # B = M = 16384, k = 32 as one launch 29.89 ms on an MI355X on the slower
+    # of the two models measured (hgbt 500 x depth 6, 3.1 M co-memberships
+    # per row; the flagship RF 500 x depth 16 2.71 ms). The caps allow no
+    # larger call, so today no call is sliced. The time follows the length of
+    # the leaf lists, so a shallower forest than depth 6 would take longer.
+    PROX_LAUNCH_ROWS = 16384
 
     def __init__(
         self,
@@ -285,6 +297,9 @@ class ScoringEngine:
         # knn_outliers: the last (reference, k) seen: its embedding, device
         # copy and leave-one-out neighbour distances
         self._knn_ref = None
+        # proximity: the last (reference, k) seen: its leaf table, inverted
+        # index and leave-one-out counts
+        self._prox_ref = None
         if device == "cuda":
             self._init_gpu()
 
@@ -1745,6 +1760,130 @@ class ScoringEngine:
         if reference is not None:
             reference = encode_batch(reference, self.packed.vocabs)
         return self.knn_outliers(codes, nums, reference=reference, **kw)
+
+    # ------------------------------------------------------- forest proximity
+    def proximity(
+        self,
+        codes: np.ndarray,
+        nums: np.ndarray,
+        reference=None,
+        k: int = 10,
+        score: str = "kth",
+        fpr: float = 0.05,
+        neighbors: bool = True,
+    ) -> dict:
+        """Breiman's forest proximity of a batch against a reference sample
+        (creditcore/proximity.py holds the definition): the proximity of two
+        rows is the share of the classifier's trees in which they end in the
+        same leaf. Per batch row the k reference rows of highest proximity,
+        ``instance_score`` = 1 - the proximity of the k-th (``score="mean"``:
+        1 - the mean of the k), ``threshold`` the ``1 - fpr`` quantile of the
+        reference's own leave-one-out scores, ``is_outlier`` their comparison.
+
+        ``reference`` defaults to the pack's background sample
+        (ExplainUnavailable without one); ``(codes, nums)`` overrides it.
+        Leaves and neighbours come from forest_leaf_kernel and
+        forest_prox_topk_kernel on a GPU engine, from cpu_ref.forest_leaves_cpu
+        and cpu_ref.forest_prox_topk_cpu on a CPU engine; both are integer, so
+        the engines agree exactly. Returns ``instance_score`` f64[B],
+        ``is_outlier`` i8[B], ``threshold``, ``k``, ``score``, ``fpr``, ``n``,
+        ``n_ref``, ``n_trees`` and, with ``neighbors``, ``neighbor_index``
+        i32[B, k] (row numbers of the reference sample, closest first, ties
+        to the lower row) and ``neighbor_proximity`` f64[B, k]. The scoring
+        session is not touched. Caps (creditcore/proximity.py) raise
+        ExplainTooLarge; bad arguments raise ValueError."""
+        from . import proximity as px
+
+        p = self.packed
+        codes, nums = px.check_rows(codes, nums, "batch", 1)
+        if len(codes) > px.PROX_MAX_ROWS:
+            raise ExplainTooLarge(
+                f"proximity is capped at {px.PROX_MAX_ROWS} batch rows (got {len(codes)})"
+            )
+        if p.cls_n_trees > px.PROX_MAX_TREES:
+            raise ExplainTooLarge(
+                f"proximity is capped at {px.PROX_MAX_TREES} trees (the model has {p.cls_n_trees})"
+            )
+        if reference is None:
+            if p.bg_codes is None or p.bg_nums is None:
+                raise ExplainUnavailable(
+                    "model was packed without a background sample; re-train and "
+                    "re-pack, or pass reference=(codes, nums)"
+                )
+            reference = (p.bg_codes, p.bg_nums)
+        ref_codes, ref_nums = px.check_rows(reference[0], reference[1], "reference", 2)
+        if len(ref_codes) > px.PROX_MAX_REFERENCE:
+            raise ExplainTooLarge(
+                f"proximity is capped at {px.PROX_MAX_REFERENCE} reference rows "
+                f"(got {len(ref_codes)})"
+            )
+        k, score, fpr = px.check_args(k, score, fpr, len(ref_codes))
+        with self._explain_lock:
+            ref = self._prox_reference(ref_codes, ref_nums, k)
+            count, idx = self._prox_topk(self._prox_leaves(codes, nums), ref, k, False)
+        return px.result(
+            count, idx, ref["loo_count"], p.cls_n_trees, k, score, fpr, bool(neighbors)
+        )
+
+    def _prox_reference(self, ref_codes, ref_nums, k: int) -> dict:
+        """Leaf table, inverted index (GPU) and leave-one-out counts of a
+        reference sample, kept for the last (sample, k) seen; the caller
+        holds _explain_lock."""
+        import hashlib
+
+        key = (hashlib.sha1(ref_codes.tobytes() + ref_nums.tobytes()).digest(), k)
+        if self._prox_ref is None or self._prox_ref["key"] != key:
+            leaf = self._prox_leaves(ref_codes, ref_nums)
+            ref = {"key": key, "leaf": leaf}
+            if self.device == "cuda":
+                from .ops import gpu
+
+                ref["index"] = gpu.prox_index(leaf, len(self.packed.cls_nodes))
+            ref["loo_count"], _ = self._prox_topk(leaf, ref, k, True)
+            self._prox_ref = ref
+        return self._prox_ref
+
+    def _prox_leaves(self, codes: np.ndarray, nums: np.ndarray):
+        """leaf[R, T] of the rows on this engine's device (numpy on a CPU
+        engine, a device tensor on a GPU engine); the caller holds
+        _explain_lock."""
+        if self.device != "cuda":
+            return cpu_ref.forest_leaves_cpu(
+                self.packed, codes, cpu_ref.impute_nums(self.packed, nums)
+            )
+        import torch
+
+        from .ops import gpu
+
+        dev = torch.device("cuda", self.device_index)
+        m = self._forest_dev()
+        with torch.cuda.device(dev):
+            return gpu.forest_leaves(
+                torch.from_numpy(codes).to(dev), torch.from_numpy(nums).to(dev), m
+            )
+
+    def _prox_topk(self, leaf_batch, ref: dict, k: int, exclude_self: bool):
+        """(count i32[B, k], idx i32[B, k]) of the batch's leaf table against
+        the reference on this engine's device."""
+        if self.device != "cuda":
+            return cpu_ref.forest_prox_topk_cpu(leaf_batch, ref["leaf"], k, exclude_self)
+        import torch
+
+        from .ops import gpu
+
+        with torch.cuda.device(torch.device("cuda", self.device_index)):
+            return gpu.forest_prox_topk(
+                leaf_batch, ref["index"], k, exclude_self,
+                launch_rows=int(self.PROX_LAUNCH_ROWS),
+            )
+
+    def proximity_records(self, records, reference=None, **kw) -> dict:
+        """proximity on a request body (list of dicts / DataFrame);
+        ``reference`` likewise, encoded with the same vocabulary."""
+        codes, nums = encode_batch(records, self.packed.vocabs)
+        if reference is not None:
+            reference = encode_batch(reference, self.packed.vocabs)
+        return self.proximity(codes, nums, reference=reference, **kw)
 
     def permutation_importance_records(self, records, labels, **kw) -> dict:
         """permutation_importance on a request body (list of dicts /

@@ -1361,3 +1361,71 @@ def knn_topk_cpu(
         idx[a:e] = order
         d2[a:e] = np.take_along_axis(d, order, axis=1)
     return d2, idx
+
+
+def forest_leaves_cpu(packed: PackedModel, codes: np.ndarray, nums_imp: np.ndarray) -> np.ndarray:
+    """i32[R, T]: the absolute index into ``cls_nodes`` of the leaf every row
+    reaches in every classifier tree (creditcore/proximity.py;
+    forest_leaf_kernel on the GPU). Level-synchronous over all (tree, row)
+    pairs like _traverse_forest, with the compares of forest_raw_cpu."""
+    nodes, off = packed.cls_nodes, packed.cls_tree_offsets
+    fc, fk = packed.feat_col, packed.feat_code
+    bits = nodes[:, 1].view(np.float32)
+    n_rows, T = len(codes), len(off) - 1
+    base = np.repeat(off[:-1].astype(np.int64), n_rows)
+    cur = base.copy()
+    rows = np.tile(np.arange(n_rows, dtype=np.int64), T)
+    alive = np.flatnonzero(nodes[cur, 0] >= 0)
+    while len(alive):
+        nidx = cur[alive]
+        feat = nodes[nidx, 0]
+        col, code, r = fc[feat], fk[feat], rows[alive]
+        cat = code >= 0
+        v = np.empty(len(alive), dtype=np.float32)
+        v[cat] = (codes[r[cat], col[cat]] == code[cat]).astype(np.float32)
+        v[~cat] = nums_imp[r[~cat], col[~cat]]
+        nxt = np.where(v <= bits[nidx], nodes[nidx, 2], nodes[nidx, 3])
+        cur[alive] = base[alive] + nxt  # children are tree-relative
+        alive = alive[nodes[cur[alive], 0] >= 0]
+    return np.ascontiguousarray(cur.reshape(T, n_rows).T, dtype=np.int32)
+
+
+def forest_prox_topk_cpu(
+    leaf_batch: np.ndarray,
+    leaf_ref: np.ndarray,
+    k: int,
+    exclude_self: bool = False,
+    max_bytes: int = 64 << 20,
+):
+    """The k reference rows that share most leaves with every batch row
+    (creditcore/proximity.py; forest_prox_topk_kernel on the GPU) as
+    ``(count i32[B, k], idx i32[B, k])``, straight from the definition:
+    ``count[i, j] = #{t : leaf_batch[i, t] == leaf_ref[j, t] >= 0}``, the k
+    largest per row in the order (count descending, j ascending), so rows that
+    share nothing fill the list lowest j first. ``exclude_self`` leaves out
+    the pair j == i by index (both sides must then be the same rows). Chunked
+    over batch rows: it never holds more than ``max_bytes`` of compares."""
+    lb = np.asarray(leaf_batch, dtype=np.int32)
+    lr = np.asarray(leaf_ref, dtype=np.int32)
+    if lb.ndim != 2 or lr.ndim != 2 or lb.shape[1] != lr.shape[1]:
+        raise ValueError("leaf_batch must be [B, T] and leaf_ref [M, T]")
+    b, m = len(lb), len(lr)
+    if exclude_self and (lb.shape != lr.shape or not np.array_equal(lb, lr)):
+        raise ValueError("exclude_self needs the same rows on both sides")
+    k = int(k)
+    if not 1 <= k <= m - (1 if exclude_self else 0):
+        raise ValueError(f"k must be in [1, {m - (1 if exclude_self else 0)}] (got {k})")
+    count = np.empty((b, k), dtype=np.int32)
+    idx = np.empty((b, k), dtype=np.int32)
+    step = max(1, int(max_bytes) // max(1, m * lb.shape[1]))
+    for a in range(0, b, step):
+        e = min(a + step, b)
+        part = lb[a:e, None, :]
+        c = ((part == lr[None, :, :]) & (part >= 0)).sum(axis=-1, dtype=np.int64)
+        if exclude_self:
+            c[np.arange(e - a), np.arange(a, e)] = -1
+        # a stable sort of -count is the lexsort on (-count, j)
+        order = np.argsort(-c, axis=1, kind="stable")[:, :k]
+        idx[a:e] = order
+        count[a:e] = np.take_along_axis(c, order, axis=1)
+    return count, idx

@@ -133,6 +133,78 @@ def knn_topk(
             np.concatenate([p[1].cpu().numpy() for p in parts]))
 
 
+def forest_leaves(codes, nums, forest: dict):
+    """forest_leaves of the extension on device tensors: leaf i32[R, T] on the
+    device, the absolute node index of the leaf every row reaches in every
+    classifier tree. ``forest`` holds the classifier tables as forest_sweep
+    takes them."""
+    return ext().forest_leaves(
+        codes,
+        nums,
+        forest["cls_nodes"],
+        forest["cls_off"],
+        forest["feat_col"],
+        forest["feat_code"],
+        forest["medians"],
+    )
+
+
+def prox_index(leaf_ref, n_nodes: int) -> dict:
+    """The inverted index of a reference's leaf table leaf_ref i32[M, T] (on
+    the device): ``leaf_start`` i32[n_nodes + 1], a CSR keyed by absolute node
+    index, and ``leaf_rows`` i16[<= M T], the reference rows of each leaf
+    (below 16384; the kernel reads them unsigned). Entries of -1 (trees the
+    leaf kernel skipped) are left out. Plain torch on the device: the order
+    inside a list does not reach the result. ``lanes_per_tree`` is the
+    kernel's default group width for these lists."""
+    import torch
+
+    from ..proximity import lanes_per_tree
+
+    m, t = int(leaf_ref.shape[0]), int(leaf_ref.shape[1])
+    flat = leaf_ref.reshape(-1).to(torch.int64)
+    order = torch.argsort(flat)
+    n_skipped = int((flat < 0).sum())
+    rows = torch.div(order[n_skipped:], t, rounding_mode="floor").to(torch.int16)
+    sizes = torch.bincount(flat[order[n_skipped:]], minlength=int(n_nodes))[: int(n_nodes)]
+    start = torch.zeros(int(n_nodes) + 1, dtype=torch.int32, device=leaf_ref.device)
+    start[1:] = torch.cumsum(sizes, 0).to(torch.int32)
+    sq = float((sizes.to(torch.float64) ** 2).sum())
+    return {
+        "leaf_start": start,
+        "leaf_rows": rows.contiguous(),
+        "n_ref": m,
+        "lanes_per_tree": lanes_per_tree(sq, int(rows.numel())),
+    }
+
+
+def forest_prox_topk(
+    leaf_batch, index: dict, k: int, exclude_self: bool = False,
+    lanes_per_tree: int = 0, launch_rows: int = 0,
+):
+    """forest_prox_topk of the extension: the k reference rows sharing most
+    leaves with every row of leaf_batch i32[B, T] (on the device) as numpy
+    ``(count i32[B, k], idx i32[B, k])`` in the order (count descending, j
+    ascending). ``index`` is prox_index of the reference's leaf table;
+    ``lanes_per_tree`` (a power of two up to 64; 0 takes the index's) does
+    not change the result; ``launch_rows`` > 0 runs it as several launches
+    over slices of that many batch rows."""
+    import numpy as np
+
+    b = int(leaf_batch.shape[0])
+    lanes = int(lanes_per_tree) or int(index["lanes_per_tree"])
+    step = int(launch_rows) if launch_rows and launch_rows < b else b
+    parts = [
+        ext().forest_prox_topk(leaf_batch, index["leaf_start"], index["leaf_rows"],
+                               int(index["n_ref"]), int(k), bool(exclude_self), lanes,
+                               a, min(step, b - a))
+        for a in range(0, b, step)
+    ]
+    # D2H copies synchronize
+    return (np.concatenate([p[0].cpu().numpy() for p in parts]),
+            np.concatenate([p[1].cpu().numpy() for p in parts]))
+
+
 def bin_select(x, f0: int, f1: int, max_bins: int, launch_rows: int):
     """bin_select of the extension on the device matrix ``x`` f32[N, F]: the
     radix-select summary of the columns [f0, f1). Returns ``(keys, state)``:

@@ -447,6 +447,42 @@ class KnnOutlierOutput(BaseModel):
     neighbor_distance: list[list[float]] | None = None
 
 
+class ProximityInput(BaseModel):
+    """POST /explain/proximity request: the records as /score takes them, the
+    number of neighbours, the score (``kth`` or ``mean``), the false-positive
+    rate behind the threshold, and whether to return the neighbours."""
+
+    records: list[dict]
+    k: int = 10
+    score: str = "kth"
+    fpr: float = 0.05
+    neighbors: bool = True
+
+    model_config = ConfigDict(extra="ignore")
+
+
+class ProximityOutput(BaseModel):
+    """POST /explain/proximity response: per record 1 - the forest proximity
+    of its k-th closest row of the packed reference sample (or 1 - the mean of
+    the k proximities) and its comparison with ``threshold``, the ``1 - fpr``
+    quantile of the sample's own leave-one-out scores. ``neighbor_index``
+    holds row numbers of the reference sample, closest first;
+    ``neighbor_proximity`` the share of the ``n_trees`` trees in which record
+    and neighbour end in the same leaf."""
+
+    instance_score: list[float]
+    is_outlier: list[int]
+    threshold: float
+    k: int
+    score: str
+    fpr: float
+    n: int
+    n_ref: int
+    n_trees: int
+    neighbor_index: list[list[int]] | None = None
+    neighbor_proximity: list[list[float]] | None = None
+
+
 # The one-record CI smoke-test fixture (reference app/sample-request.json).
 SAMPLE_REQUEST: list[dict] = [
     {

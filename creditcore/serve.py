@@ -55,6 +55,8 @@ from .schema import (
     ModelOutput,
     PdpOutput,
     PdpRequest,
+    ProximityInput,
+    ProximityOutput,
 )
 from .utils import logging as reqlog
 from .utils.metrics import Metrics
@@ -1089,6 +1091,69 @@ def create_app(cfg: ServeConfig | None = None) -> FastAPI:
             metrics.observe_error()
             pool.report_fail(idx)
             raise HTTPException(status_code=500, detail=f"knn outliers failed: {e}")
+        metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
+        return _json_response(
+            {key: v.tolist() if isinstance(v, np.ndarray) else v for key, v in out.items()}
+        )
+
+    @app.post("/explain/proximity", response_model=ProximityOutput)
+    async def explain_proximity(req: ProximityInput):
+        """Forest proximity of the posted records against the model's packed
+        background sample (ScoringEngine.proximity): the sample rows the
+        classifier treats most like each record, and a model-aware outlier
+        score. Stateless: the scoring session is not touched. One attempt on
+        one live replica; bypasses the micro-batcher."""
+        import asyncio
+
+        from .proximity import PROX_MAX_ROWS
+
+        metrics: Metrics = state["metrics"]
+        engines = state["engines"]
+        pool: ReplicaPool = state["pool"]
+        packed = engines[0].packed
+        if packed.bg_codes is None or packed.bg_nums is None:
+            raise HTTPException(
+                status_code=501,
+                detail="the served model was packed without a background sample; "
+                "re-train and re-pack it to enable /explain/proximity",
+            )
+        if len(req.records) > PROX_MAX_ROWS:
+            raise HTTPException(
+                status_code=413, detail=f"/explain/proximity takes at most {PROX_MAX_ROWS} rows"
+            )
+        if len(req.records) < 1:
+            raise HTTPException(
+                status_code=422, detail="/explain/proximity needs at least one row"
+            )
+        try:
+            codes, nums = encode_batch(req.records, packed.vocabs)
+        except (ValueError, TypeError, KeyError) as e:
+            raise HTTPException(status_code=422, detail=f"bad record: {e}")
+        try:
+            idx = pool.pick()
+        except RuntimeError:
+            metrics.observe_error()
+            raise HTTPException(status_code=503, detail="no healthy replicas")
+        t0 = time.perf_counter()
+
+        def call():
+            return engines[idx].proximity(
+                codes, nums, k=req.k, score=req.score, fpr=req.fpr, neighbors=req.neighbors
+            )
+
+        try:
+            out = await asyncio.get_running_loop().run_in_executor(None, call)
+            pool.report_ok(idx)
+        except ExplainTooLarge as e:  # the request's fault, not the replica's
+            raise HTTPException(status_code=413, detail=str(e))
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        except ExplainUnavailable as e:
+            raise HTTPException(status_code=501, detail=str(e))
+        except Exception as e:
+            metrics.observe_error()
+            pool.report_fail(idx)
+            raise HTTPException(status_code=500, detail=f"proximity failed: {e}")
         metrics.observe_request(len(codes), (time.perf_counter() - t0) * 1e3)
         return _json_response(
             {key: v.tolist() if isinstance(v, np.ndarray) else v for key, v in out.items()}

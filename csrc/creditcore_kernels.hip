@@ -5636,6 +5636,424 @@ std::vector<torch::Tensor> knn_topk(torch::Tensor z_batch, torch::Tensor z_ref,
 }
 
 // ---------------------------------------------------------------------------
+// Forest proximity (creditcore/proximity.py): c(i, j) = the number of trees in
+// which batch row i and reference row j end in the same leaf, and per batch
+// row the k reference rows in the order (c descending, j ascending). Neither
+// the B x M count matrix nor a one-hot over (tree, leaf) is ever held; the
+// matrix cores have no part in it (leaf equality is not a bilinear form over
+// a small alphabet).
+//
+//   forest_leaf_kernel       leaf[r, t] = absolute node index of the leaf row
+//                            r reaches in tree t (both sides use it)
+//   host (ops/gpu.py)        inverted index of the reference's leaf table:
+//                            leaf_start[n_nodes + 1] (CSR by node index) and
+//                            leaf_rows (the reference rows of each leaf, u16)
+//   forest_prox_topk_kernel  one block per batch row: counts by walking the
+//                            T row lists of its leaves, then a counting select
+// ---------------------------------------------------------------------------
+
+// Work split as forest_whatif_kernel: one thread owns a row, one wave per
+// block, rows staged column-major in LDS with fused imputation (own slots
+// only, so no barrier and threads past the last row leave at once).
+// blockIdx.y picks a chunk of trees_per_chunk consecutive trees; LEAF_ILP of
+// them are in flight per thread. Every entry of leaf[R, T] is written by a
+// plain store.
+//
+// Bounds by construction (the note on forest_ale_kernel): a tree whose
+// [base, base + size) does not lie inside the node table is skipped, a node
+// index is compared unsigned against the tree's size before every load,
+// source columns are clamped and the walk loop runs at most `size` times. A
+// skipped tree, a bad child index, a feature index outside the table and a
+// walk the loop bound stopped on a split all write -1, which
+// forest_prox_topk_kernel never counts.
+#define LEAF_BLOCK 64
+#define LEAF_ILP 4
+
+__global__ __launch_bounds__(LEAF_BLOCK) void forest_leaf_kernel(
+    const short* __restrict__ codes,    // [R, N_CAT]
+    const float* __restrict__ nums,     // [R, N_NUM], NaNs not yet imputed
+    const float* __restrict__ medians,  // [N_NUM]
+    const int4* __restrict__ nodes,     // [n_nodes] {feat, bits, left, right}
+    const int* __restrict__ tree_off,   // [T+1]
+    int n_trees,
+    unsigned n_nodes,
+    const int* __restrict__ feat_col,   // [F]
+    const int* __restrict__ feat_code,  // [F]
+    unsigned n_feat,
+    int n_rows,
+    int trees_per_chunk,
+    int* __restrict__ leaf)             // [R, T]; every entry is written
+{
+  __shared__ short s_codes[N_CAT * LEAF_BLOCK];
+  __shared__ float s_nums[N_NUM * LEAF_BLOCK];
+
+  const int tid = threadIdx.x;
+  const int row = blockIdx.x * LEAF_BLOCK + tid;
+  if (row >= n_rows) return;  // no barrier below: own LDS slots only
+
+#pragma unroll
+  for (int c = 0; c < N_CAT; ++c)
+    s_codes[c * LEAF_BLOCK + tid] = codes[(size_t)row * N_CAT + c];
+#pragma unroll
+  for (int c = 0; c < N_NUM; ++c) {
+    const float v = nums[(size_t)row * N_NUM + c];
+    s_nums[c * LEAF_BLOCK + tid] = isnan(v) ? medians[c] : v;
+  }
+
+  const int4 dead = make_int4(-1, 0, 0, 0);
+  const int t_begin = blockIdx.y * trees_per_chunk;
+  const int t_end = min(t_begin + trees_per_chunk, n_trees);
+  int* __restrict__ out = leaf + (size_t)row * n_trees;
+
+  for (int t = t_begin; t < t_end; t += LEAF_ILP) {
+    int4 nd[LEAF_ILP];
+    int base[LEAF_ILP], cur[LEAF_ILP];
+    unsigned size[LEAF_ILP];
+    unsigned longest = 0;
+#pragma unroll
+    for (int s = 0; s < LEAF_ILP; ++s) {
+      base[s] = 0;
+      size[s] = 0;
+      cur[s] = -1;
+      nd[s] = dead;
+      if (t + s < t_end) {
+        const int b0 = tree_off[t + s];
+        const int sz = tree_off[t + s + 1] - b0;
+        if (b0 >= 0 && sz > 0 && (unsigned)b0 + (unsigned)sz <= n_nodes) {
+          base[s] = b0;
+          size[s] = (unsigned)sz;
+          cur[s] = b0;
+          nd[s] = nodes[b0];
+        }
+      }
+      longest = max(longest, size[s]);
+    }
+    bool any = true;
+    for (unsigned it = 0; it < longest && any; ++it) {
+      any = false;
+#pragma unroll
+      for (int s = 0; s < LEAF_ILP; ++s) {
+        if ((unsigned)nd[s].x < n_feat) {
+          const int fcol = feat_col[nd[s].x];
+          const int code = feat_code[nd[s].x];
+          const float v = (code >= 0)
+              ? ((s_codes[min((unsigned)fcol, (unsigned)(N_CAT - 1)) * LEAF_BLOCK + tid] ==
+                  (short)code) ? 1.0f : 0.0f)
+              : s_nums[min((unsigned)fcol, (unsigned)(N_NUM - 1)) * LEAF_BLOCK + tid];
+          const int rel = (v <= __int_as_float(nd[s].y)) ? nd[s].z : nd[s].w;
+          if ((unsigned)rel < size[s]) {
+            cur[s] = base[s] + rel;
+            nd[s] = nodes[cur[s]];
+          } else {
+            cur[s] = -1;
+            nd[s] = dead;
+          }
+          any = true;
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < LEAF_ILP; ++s)
+      if (t + s < t_end) out[t + s] = (nd[s].x < 0) ? cur[s] : -1;
+  }
+}
+
+// leaf i32[R, T] of the R rows in every classifier tree (forest_leaf_kernel).
+// Stateless like forest_ale; the kernel bounds-checks the forest tables.
+torch::Tensor forest_leaves(
+    torch::Tensor codes, torch::Tensor nums,
+    torch::Tensor cls_nodes, torch::Tensor cls_off,
+    torch::Tensor feat_col, torch::Tensor feat_code,
+    torch::Tensor medians, int64_t block_target)
+{
+  check_inputs(codes, nums);
+  TORCH_CHECK(block_target >= 1 && block_target <= 65535, "bad block_target");
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType st, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == codes.device(), name,
+                " must be on the inputs' GPU");
+    TORCH_CHECK(t.scalar_type() == st && t.is_contiguous(), name,
+                " has the wrong dtype or is not contiguous");
+  };
+  on_dev(nums, torch::kFloat32, "nums");
+  on_dev(cls_nodes, torch::kInt32, "cls_nodes");
+  on_dev(cls_off, torch::kInt32, "cls_off");
+  on_dev(feat_col, torch::kInt32, "feat_col");
+  on_dev(feat_code, torch::kInt32, "feat_code");
+  on_dev(medians, torch::kFloat32, "medians");
+  TORCH_CHECK(cls_nodes.dim() == 2 && cls_nodes.size(1) == 4, "cls_nodes must be [n, 4]");
+  TORCH_CHECK(cls_nodes.size(0) < (int64_t(1) << 31), "too many nodes");
+  TORCH_CHECK(feat_col.numel() == feat_code.numel(), "feat_col/feat_code size mismatch");
+  TORCH_CHECK(medians.numel() == N_NUM, "medians must have N_NUM entries");
+  TORCH_CHECK(cls_off.dim() == 1 && cls_off.numel() >= 2, "forest has no trees");
+
+  const int64_t R = codes.size(0);
+  const int64_t T = cls_off.size(0) - 1;
+  TORCH_CHECK(R >= 1, "forest_leaves needs at least one row");
+  TORCH_CHECK(R * T < (int64_t(1) << 31), "too many (row, tree) pairs");
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)codes.get_device());
+  auto leaf = torch::empty({R, T},
+      torch::TensorOptions().dtype(torch::kInt32).device(codes.device()));
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  const int row_blocks = ceil_div((int)R, LEAF_BLOCK);
+  // One-wave blocks; the trees are cut into chunks (whole LEAF_ILP groups)
+  // until the grid has about block_target blocks.
+  const int groups = ceil_div((int)T, LEAF_ILP);
+  const int chunks = (int)std::max<int64_t>(
+      1, std::min<int64_t>(ceil_div((int)block_target, row_blocks), groups));
+  const int per_chunk = ceil_div(groups, chunks) * LEAF_ILP;
+  hipLaunchKernelGGL(forest_leaf_kernel,
+      dim3(row_blocks, ceil_div((int)T, per_chunk)), dim3(LEAF_BLOCK), 0, stream,
+      codes.data_ptr<short>(), nums.data_ptr<float>(), medians.data_ptr<float>(),
+      reinterpret_cast<const int4*>(cls_nodes.data_ptr<int>()),
+      cls_off.data_ptr<int>(), (int)T, (unsigned)cls_nodes.size(0),
+      feat_col.data_ptr<int>(), feat_code.data_ptr<int>(), (unsigned)feat_col.numel(),
+      (int)R, per_chunk, leaf.data_ptr<int>());
+  HIP_CHECK(hipGetLastError());
+  return leaf;
+}
+
+// Counts and selection, one 256-thread block per batch row i.
+//
+// LDS (dynamic, sized by the launcher to M and T): the row's M counters as
+// packed u16 pairs, ceil(M / 2) u32 (32 KiB at M = 16384), then T + 1
+// histogram bins (16 KiB at T = 4096), zeroed by the block; PROX_MAX_K keys
+// and three words of state are static. c <= T < 65536, so an add of 1 or of
+// 1 << 16 never carries from the low half into the high one.
+//
+// Count phase. A group of lanes_per_tree lanes (a power of two, 1 to 64; the
+// launcher picks it from the lengths of the lists a row meets) takes tree
+// t = group, group + n_groups, ...: it reads the row's leaf id, the leaf's
+// range in the index, and strides over the range, adding into the counter of
+// every reference row listed. The adds are integer LDS atomics, so the counts
+// do not depend on their order, on lanes_per_tree or on timing. Work per row
+// is the number of co-memberships, sum_t |list of leaf_t|, not T x M. A leaf
+// id outside [0, n_nodes) (the -1 of a skipped tree), a range outside the
+// list and a row number outside [0, M) are dropped, not counted.
+//
+// Selection phase, a counting select:
+//   1. histogram of the counter values over j (j == self left out); zeros,
+//      which most counters hold, are added once per wave from a ballot;
+//   2. wave 0 scans the bins downward from T, 64 at a time, for the largest
+//      c* with #{j : c_j >= c*} >= k, and notes n_above = #{j : c_j > c*} < k;
+//   3. every j with c_j > c* takes a key slot (LDS atomic, any order);
+//   4. wave 0 scans j upward by ballot and takes the lowest j with
+//      c_j == c* until k keys are held, then stops;
+//   5. wave 0 ranks the k keys (T - c) << 14 | j (distinct, as j is) and
+//      stores count[i, rank] and idx[i, rank].
+// The launcher guarantees k <= M - exclude_self, so c* exists (zeros fill the
+// list, lowest j first).
+#define PROX_BLOCK 256
+#define PROX_MAX_K 32
+#define PROX_UNROLL 4         // list entries a lane loads before it adds them
+#define PROX_MAX_ROWS 16384  // 14-bit j in the key, u16 in leaf_rows
+#define PROX_MAX_TREES 4096   // (T - c) << 14 stays inside 27 bits
+
+// Counter j of the packed pairs; never above T on a sound index, and clamped
+// so that a bad one cannot leave the histogram or the key's bit field.
+__device__ __forceinline__ unsigned prox_count_of(const unsigned* cnt, int j, int n_trees) {
+  return min((cnt[j >> 1] >> ((j & 1) << 4)) & 0xffffu, (unsigned)n_trees);
+}
+
+__global__ __launch_bounds__(PROX_BLOCK) void forest_prox_topk_kernel(
+    const int* __restrict__ leaf_batch,            // [B, T]
+    const int* __restrict__ leaf_start,            // [n_nodes + 1]
+    const unsigned short* __restrict__ leaf_rows,  // [n_list]
+    unsigned n_nodes,
+    int n_list,
+    int n_trees,
+    int n_ref,          // M
+    int k,
+    int lanes_per_tree,
+    int row_begin,
+    int exclude_self,
+    int* __restrict__ count,  // [rows of the launch, k]; every entry is written
+    int* __restrict__ idx)    // [rows of the launch, k]; every entry is written
+{
+  extern __shared__ unsigned prox_lds[];
+  __shared__ unsigned s_keys[PROX_MAX_K];
+  __shared__ int s_cstar, s_above, s_held;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int i = row_begin + blockIdx.x;
+  const int self = exclude_self ? i : -1;
+  const int n_pairs = (n_ref + 1) >> 1;
+  unsigned* cnt = prox_lds;             // [n_pairs]
+  unsigned* hist = prox_lds + n_pairs;  // [n_trees + 1]
+
+  for (int w = tid; w < n_pairs + n_trees + 1; w += PROX_BLOCK) prox_lds[w] = 0u;
+  if (tid < PROX_MAX_K) s_keys[tid] = 0xffffffffu;
+  if (tid == 0) {
+    s_held = 0;
+    s_cstar = 0;
+    s_above = 0;
+  }
+  __syncthreads();
+
+  // ---- count
+  {
+    const int sub = tid & (lanes_per_tree - 1);
+    const int n_groups = PROX_BLOCK / lanes_per_tree;
+    const int* __restrict__ mine = leaf_batch + (size_t)i * n_trees;
+    for (int t = tid / lanes_per_tree; t < n_trees; t += n_groups) {
+      const int lf = mine[t];
+      if ((unsigned)lf >= n_nodes) continue;
+      const int p0 = leaf_start[lf];
+      const int p1 = min(leaf_start[lf + 1], n_list);
+      if (p0 < 0) continue;
+      // PROX_UNROLL independent loads in flight per lane, then their adds: a
+      // long list is bound by the latency of its 2-byte loads otherwise
+      for (int p = p0 + sub; p < p1; p += PROX_UNROLL * lanes_per_tree) {
+        unsigned j[PROX_UNROLL];
+#pragma unroll
+        for (int u = 0; u < PROX_UNROLL; ++u) {
+          const int q = p + u * lanes_per_tree;
+          j[u] = (q < p1) ? (unsigned)leaf_rows[q] : 0xffffffffu;
+        }
+#pragma unroll
+        for (int u = 0; u < PROX_UNROLL; ++u)
+          if (j[u] < (unsigned)n_ref) atomicAdd(&cnt[j[u] >> 1], 1u << ((j[u] & 1u) << 4));
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- 1. histogram of the counts (whole waves stay in the loop: ballot)
+  for (int j0 = wave * 64; j0 < n_ref; j0 += PROX_BLOCK) {
+    const int j = j0 + lane;
+    const bool live = j < n_ref && j != self;
+    const unsigned c = live ? prox_count_of(cnt, j, n_trees) : 0u;
+    const unsigned long long zeros = __ballot(live && c == 0u);
+    if (live && c != 0u) atomicAdd(&hist[c], 1u);
+    if (lane == 0 && zeros) atomicAdd(&hist[0], (unsigned)__popcll(zeros));
+  }
+  __syncthreads();
+
+  // ---- 2. c* and n_above
+  if (wave == 0) {
+    int above = 0;  // #{j : c_j > top of this step}, wave-uniform
+    for (int top = n_trees; top >= 0; top -= 64) {
+      const int c = top - lane;
+      const int h = (c >= 0) ? (int)hist[c] : 0;
+      int incl = h;  // inclusive scan over the lanes: bins top .. top - lane
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(incl, d);
+        if (lane >= d) incl += up;
+      }
+      const unsigned long long hit = __ballot(c >= 0 && above + incl >= k);
+      if (hit) {
+        const int first = __ffsll((long long)hit) - 1;
+        if (lane == first) {
+          s_cstar = c;
+          s_above = above + incl - h;
+        }
+        break;
+      }
+      above += __shfl(incl, 63);
+    }
+  }
+  __syncthreads();
+  const unsigned cstar = (unsigned)s_cstar;
+  const int n_above = s_above;
+
+  // ---- 3. every j above c*
+  if (n_above > 0) {
+    for (int j = tid; j < n_ref; j += PROX_BLOCK) {
+      const unsigned c = prox_count_of(cnt, j, n_trees);
+      if (c > cstar && j != self) {
+        const int pos = atomicAdd(&s_held, 1);
+        if (pos < PROX_MAX_K) s_keys[pos] = (((unsigned)n_trees - c) << 14) | (unsigned)j;
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- 4. the lowest j at c*
+  if (wave == 0) {
+    int held = n_above;  // wave-uniform
+    for (int j0 = 0; j0 < n_ref && held < k; j0 += 64) {
+      const int j = j0 + lane;
+      const bool hit = j < n_ref && j != self && prox_count_of(cnt, j, n_trees) == cstar;
+      const unsigned long long m = __ballot(hit);
+      const int rank = __popcll(m & ((1ull << lane) - 1ull));
+      if (hit && held + rank < k)
+        s_keys[held + rank] = (((unsigned)n_trees - cstar) << 14) | (unsigned)j;
+      held = min(held + (int)__popcll(m), k);
+    }
+  }
+  __syncthreads();
+
+  // ---- 5. order the k keys
+  if (wave == 0 && lane < k) {
+    const unsigned key = s_keys[lane];
+    int rank = 0;
+    for (int q = 0; q < k; ++q) rank += (s_keys[q] < key) ? 1 : 0;
+    const size_t at = (size_t)blockIdx.x * k + rank;
+    count[at] = n_trees - (int)(key >> 14);
+    idx[at] = (int)(key & 0x3fffu);
+  }
+}
+
+// The k reference rows that share most leaves with batch rows [row_begin,
+// row_begin + row_count): (count i32[row_count, k], idx i32[row_count, k]) in
+// the order (count descending, j ascending). leaf_batch i32[B, T] is
+// forest_leaves of the batch; leaf_start i32[n_nodes + 1] and leaf_rows
+// i16[n_list] (row numbers below 16384, read unsigned) the inverted index of
+// forest_leaves of the M reference rows. exclude_self leaves out the pair
+// j == i (global row numbers; the batch must then be the reference).
+std::vector<torch::Tensor> forest_prox_topk(
+    torch::Tensor leaf_batch, torch::Tensor leaf_start, torch::Tensor leaf_rows,
+    int64_t n_ref, int64_t k, bool exclude_self, int64_t lanes_per_tree,
+    int64_t row_begin, int64_t row_count)
+{
+  TORCH_CHECK(leaf_batch.is_cuda() && leaf_batch.scalar_type() == torch::kInt32 &&
+              leaf_batch.dim() == 2 && leaf_batch.is_contiguous(),
+              "leaf_batch must be a contiguous i32[B, T] GPU tensor");
+  TORCH_CHECK(leaf_start.is_cuda() && leaf_start.device() == leaf_batch.device() &&
+              leaf_start.scalar_type() == torch::kInt32 && leaf_start.dim() == 1 &&
+              leaf_start.is_contiguous() && leaf_start.numel() >= 2,
+              "leaf_start must be a contiguous i32[n_nodes + 1] tensor on leaf_batch's GPU");
+  TORCH_CHECK(leaf_rows.is_cuda() && leaf_rows.device() == leaf_batch.device() &&
+              leaf_rows.scalar_type() == torch::kInt16 && leaf_rows.dim() == 1 &&
+              leaf_rows.is_contiguous(),
+              "leaf_rows must be a contiguous i16[n_list] tensor on leaf_batch's GPU");
+  const int64_t B = leaf_batch.size(0), T = leaf_batch.size(1), M = n_ref;
+  TORCH_CHECK(B >= 1 && B <= PROX_MAX_ROWS, "batch rows out of range: ", B);
+  TORCH_CHECK(M >= 1 && M <= PROX_MAX_ROWS, "reference rows out of range: ", M);
+  TORCH_CHECK(T >= 1 && T <= PROX_MAX_TREES, "trees out of range: ", T);
+  TORCH_CHECK(leaf_rows.numel() <= M * T, "leaf_rows is longer than M x T");
+  TORCH_CHECK(!exclude_self || B == M, "exclude_self needs the same rows on both sides");
+  TORCH_CHECK(k >= 1 && k <= PROX_MAX_K && k <= M - (exclude_self ? 1 : 0),
+              "k must be in [1, ", PROX_MAX_K, "] and at most the number of "
+              "reference rows a batch row can take");
+  TORCH_CHECK(lanes_per_tree >= 1 && lanes_per_tree <= 64 &&
+              (lanes_per_tree & (lanes_per_tree - 1)) == 0,
+              "lanes_per_tree must be a power of two in [1, 64]");
+  if (row_count < 0) row_count = B - row_begin;
+  TORCH_CHECK(row_begin >= 0 && row_count >= 1 && row_begin + row_count <= B,
+              "row slice must lie inside [0, B)");
+
+  c10::hip::HIPGuard guard((c10::DeviceIndex)leaf_batch.get_device());
+  auto opt = torch::TensorOptions().dtype(torch::kInt32).device(leaf_batch.device());
+  auto count = torch::empty({row_count, k}, opt);
+  auto idx = torch::empty({row_count, k}, opt);
+  const size_t lds = sizeof(unsigned) * (size_t)((M + 1) / 2 + T + 1);  // <= 48 KiB + 4 B
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(forest_prox_topk_kernel, dim3((unsigned)row_count),
+      dim3(PROX_BLOCK), lds, stream,
+      leaf_batch.data_ptr<int>(), leaf_start.data_ptr<int>(),
+      reinterpret_cast<const unsigned short*>(leaf_rows.data_ptr<int16_t>()),
+      (unsigned)(leaf_start.numel() - 1), (int)leaf_rows.numel(), (int)T, (int)M, (int)k,
+      (int)lanes_per_tree, (int)row_begin, exclude_self ? 1 : 0,
+      count.data_ptr<int>(), idx.data_ptr<int>());
+  HIP_CHECK(hipGetLastError());
+  return {count, idx};
+}
+
+// ---------------------------------------------------------------------------
 // ScoreSession — one replica's resident GPU state + a single-call scoring
 // path. Owns the model buffers in HBM, a private HIP stream, device
 // workspace and pinned staging, so one Python call per request performs:
@@ -6482,6 +6900,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("norms_ref"), py::arg("k"), py::arg("exclude_self"),
         py::arg("cols_per_block"), py::arg("row_begin") = 0,
         py::arg("row_count") = -1);
+  m.def("forest_leaves", &forest_leaves,
+        "leaf i32[R, T]: the absolute node index of the leaf every row reaches "
+        "in every classifier tree, -1 for a tree outside the node table (gfx950)",
+        py::arg("codes"), py::arg("nums"), py::arg("cls_nodes"),
+        py::arg("cls_off"), py::arg("feat_col"), py::arg("feat_code"),
+        py::arg("medians"), py::arg("block_target") = 2048);
+  m.def("forest_prox_topk", &forest_prox_topk,
+        "forest proximity: per batch row the k reference rows sharing most "
+        "leaves -> (count i32[rows, k], idx i32[rows, k]) in the order (count "
+        "desc, j asc); counts from an inverted leaf index in LDS u16 counters, "
+        "counting select, no B x M array (gfx950)",
+        py::arg("leaf_batch"), py::arg("leaf_start"), py::arg("leaf_rows"),
+        py::arg("n_ref"), py::arg("k"), py::arg("exclude_self"),
+        py::arg("lanes_per_tree") = 64, py::arg("row_begin") = 0,
+        py::arg("row_count") = -1);
+  m.attr("PROX_MAX_K") = py::int_(PROX_MAX_K);
+  m.attr("PROX_MAX_TREES") = py::int_(PROX_MAX_TREES);
   m.attr("KNN_TILE") = py::int_(KNN_TILE);
   m.attr("KNN_MAX_K") = py::int_(KNN_MAX_K);
   m.def("encode_records", &encode_records,
